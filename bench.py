@@ -10,10 +10,14 @@ read-back (jitter ladder).  Inputs are resident in HBM before the timed region.
 --gpus 1 (default): the headline is BASELINE.json configs[2] = "C3", the largest single-GPU
     configuration and the north-star target size: GPR + Matern52, N=32768, D=16, fp64 (synthetic
     X~N(0,1), y=sin(sum x)+0.1 eps from gptorch_amd.rng seed 0; sigma^2=1, ell=4, sigma_n^2=1e-2),
-    through the gptorch-compatible shell (`model.log_likelihood()`).  Keyed extras carry the other
-    single-GPU configs, each with its own config string: `c1` (N=512, with its CPU timing), `c2` (N=8192, D=8, Rbf; + `cpu_baseline`), `c4_1gpu`
+    through the gptorch-compatible shell (`model.log_likelihood()`).  A plain run sets up, warms up,
+    times --steps steps and prints the headline line only.  With --full the line also carries the
+    rooflines, the goldens, the CPU baseline and keyed extras for the other single-GPU configs, each with
+    its own config string: `c1` (N=512, with its CPU timing), `c2` (N=8192, D=8, Rbf; + `cpu_baseline`), `c4_1gpu`
     (N=65536, D=32: the 34 GB factor fits one GPU's HBM), `c5_vfe` (sparse VFE, N=1e6, M=4096) and
     `loss_backward` (one Adam step's loss()+backward()) at C2 and C3.
+--dump-outputs DIR: after the timed steps, what the last timed step returned (the LML) as DIR/lml.npy (float64);
+    the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 --gpus N>1 (launched by torch.distributed.run, one rank per GPU): STRONG scaling of
     configs[3] = "C4" (GPR + Rbf, N=65536, D=32): ONE model, its Gram matrix 2-D block-cyclic over
     all ranks (gptorch_amd/dist.py), panels exchanged by RCCL broadcasts on row / column
@@ -21,7 +25,7 @@ read-back (jitter ladder).  Inputs are resident in HBM before the timed region.
     same matrix on its own GPU alone (`single_gpu_same_run`) and every rank runs independent C2
     replicas (`replicas_c2`, labelled, not the headline).
 
-Extra objects on the JSON line (N=1):
+Extra objects on the JSON line (N=1, --full):
   roofline            -- the dominant kernel on one stream: the fp64 MFMA contraction kernel's SYRK trailing updates (the
                          lower-tile K = panel-width launch at the end of every panel; north_star's ">= 50 % of fp64
                          MFMA peak at N=32768"): algorithmic flops of those launches / their summed HIP-event time
@@ -135,6 +139,24 @@ def timed(fn, steps, warmup):
         out = fn()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / steps, out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy, float32 kept as float32, everything else as float64; at most
+    64 MB in all (an output that would not fit must be sampled by the caller, with a fixed seed)."""
+    outs = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        outs[name] = a.astype(np.float32 if a.dtype == np.float32 else np.float64, copy=False)
+    total = sum(a.nbytes for a in outs.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(path, exist_ok=True)
+    for name, a in outs.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 CPU_CHILD = r"""
@@ -427,6 +449,22 @@ def backward_leg(lib, model, w, steps):
     return out
 
 
+def headline_line(args, w, elapsed, lml):
+    """the one-GPU line's headline fields: all a plain run prints (--full adds the rest after them)."""
+    return {
+        "metric": "GP log-marginal-likelihood evals/sec (Cholesky+solve) at NxD fp64",
+        "value": args.steps / elapsed, "unit": "LML evals/s",
+        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True, "scaling": None, "vs_baseline": None,
+        "scaling_note": "one GPU: no scaling claim.  --gpus N>1 is STRONG scaling of C4 (N=65536) and carries its own "
+                        "single-GPU point (single_gpu_same_run / speedup_vs_single_gpu_same_run); c4_1gpu (--full) is that point here",
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": w["name"], "N": w["n"], "D": w["d"], "dy": w["dy"], "kernel": w["kind"], "parallelism": "1 GPU"},
+        "lml": lml,
+        "cholesky_frac_of_fp64_peak": (w["n"] ** 3 / 3.0) / (elapsed / args.steps) / 1e12 / PEAK_FP64_MFMA_TFLOPS,
+    }
+
+
 def run_single(args, device):
     from gptorch_amd import _native
     lib = _native.lib()   # raises if the HIP library is missing: no fallback
@@ -449,6 +487,11 @@ def run_single(args, device):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     lml = out.item()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"lml": out})
+    if not args.full:
+        print(json.dumps(headline_line(args, w, elapsed, lml)), flush=True)
+        return
 
     roofs = rooflines(lib, w, args.steps, step)
     attach_traffic(roofs.get("roofline"), "gemm_bytes_per_launch", args.workload)
@@ -850,19 +893,7 @@ def run_single(args, device):
         else:
             leg("loss_backward", lambda: backward_leg(lib, held["model"], w, max(2, args.steps // 4) if w["n"] <= 8192 else 2))
 
-    ms = elapsed / args.steps * 1e3
-    line = {
-        "metric": "GP log-marginal-likelihood evals/sec (Cholesky+solve) at NxD fp64",
-        "value": args.steps / elapsed, "unit": "LML evals/s",
-        "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
-        "higher_is_better": True, "scaling": None, "vs_baseline": None,
-        "scaling_note": "one GPU: no scaling claim.  --gpus N>1 is STRONG scaling of C4 (N=65536) and carries its own "
-                        "single-GPU point (single_gpu_same_run / speedup_vs_single_gpu_same_run); c4_1gpu below is that point here",
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": w["name"], "N": w["n"], "D": w["d"], "dy": w["dy"], "kernel": w["kind"], "parallelism": "1 GPU"},
-        "lml": lml,
-        "cholesky_frac_of_fp64_peak": (w["n"] ** 3 / 3.0) / (elapsed / args.steps) / 1e12 / PEAK_FP64_MFMA_TFLOPS,
-    }
+    line = headline_line(args, w, elapsed, lml)
     gl = golden_lml(w)
     if gl is not None:
         line["lml_%s_golden" % golden_source(w)] = gl
@@ -1238,6 +1269,8 @@ def run_multi(args, rank, local_rank, world, device):
             extra["fits_per_s_estimate_note"] = "1 / (50 x one distributed loss+backward): a fit = 50 Adam steps (BASELINE configs[2]); measured end to end only at N = 1 (c3_adam50)"
         guarded("dist_backward", float(wd) if wd else 12.0 * sec * (args.steps + args.warmup + 1) + 60.0, dist_backward)
     if rank == 0:
+        if args.dump_outputs:          # the headline schedule's value (every rank holds the same LML)
+            dump_outputs(args.dump_outputs, {"lml": np.float64(per_schedule[min(per_schedule, key=lambda k: per_schedule[k]["ms_per_step"])]["lml"])})
         print(line_text(), flush=True)
 
 
@@ -1311,7 +1344,12 @@ def main():
     ap.add_argument("--cpu-baseline-budget", type=float, default=90.0,
                     help="seconds the full-size CPU leg may take (1 warm-up + up to 3 timed evaluations; fewer timed ones if "
                          "3 would overrun it; 0 = always 3)")
-    ap.add_argument("--no-extras", action="store_true", help="headline + rooflines only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="(1 GPU) after the headline, everything else the line carries: rooflines, goldens, extras, CPU baseline; "
+                         "a plain run measures the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) headline + rooflines only (profiling runs)")
     ap.add_argument("--test-shared-gpu", action="store_true",
                     help="(testing the multi-rank control flow on a 1-GPU box) every rank uses cuda:0, gloo collectives")
     ap.add_argument("--schedule", default="both", choices=["both", "bcast", "mesh"],
@@ -1340,6 +1378,8 @@ def main():
         args.steps = (20 if world == 1 else 5) if big else 20
     if args.warmup is None:
         args.warmup = (3 if world == 1 else 2) if big else 3
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.test_shared_gpu:
         local_rank = 0
     torch.cuda.set_device(local_rank)
