@@ -1,8 +1,9 @@
 """Randomised parity where the driver sees it: fixed-seed, bounded slices of the sweeps under tests/sweeps/ (run by hand at
 380 cases per round, profiles/r3_sweeps_final.txt) as `-m gpu` tests.  Each slice is the sweep script itself in a child
-process (they edit module globals such as the VFE chunk size), with a fixed case count and seed; the script exits 1 on the
-first violated tolerance and prints the offending case.  The CPU oracle (oracle/gp_oracle.py) is the checker on one side of
-fuzz_parity / fuzz_vfe; fuzz_expr checks the fused expression kernels against the reference's way of composing the same
+process (they edit module globals such as the VFE chunk size), with a fixed case count and seed; the script exits 1 on a
+violated tolerance and prints the offending case.  The CPU oracle (oracle/gp_oracle.py) is the checker on one side of
+fuzz_parity / fuzz_vfe for the smooth kinds; their Exp / Matern12 / Periodic cases are judged by the same oracle with
+direct-difference distances (tests/_xref.py: the Gram-trick distances leave ~1e-8 of noise at Exp's cusp); fuzz_expr checks the fused expression kernels against the reference's way of composing the same
 tree (children's dense matrices combined by + and *, kernels.py:286-306)."""
 import os
 import subprocess
@@ -27,15 +28,17 @@ def _run(script, cases, seed, timeout):
 @pytest.mark.parametrize("seed", [11, 12])
 def test_fuzz_gpr_against_the_oracle(device, seed):
     """GPR loss, the three raw-parameter gradients and predict_f at random sizes on and around every blocking edge (16-pivot
-    blocks, 128 leaf, 1536 panel), all stationary kinds, ARD / isotropic, dy 1..4, noise 1e-3 .. 0.1
-    (gpr.py:47-117 through gptorch_amd against oracle.GPROracle)."""
+    blocks, 128 leaf, 1536 panel), ARD / isotropic, noise 1e-3 .. 0.1 (gpr.py:47-117 through gptorch_amd): 14 cases of Rbf /
+    Matern52 / Matern32 at d <= 33, dy 1..4 against oracle.GPROracle, then 7 of every stationary kind (Periodic at d = 1) at
+    d up to 64, dy up to 5 against tests/_xref.DirectGPR."""
     print(_run("fuzz_parity.py", 14, seed, 600))
 
 
 @pytest.mark.gpu
 def test_fuzz_vfe_against_the_oracle(device):
     """VFE bound, every gradient incl. the inducing points, predictions, with random chunk sizes of the streamed evaluation
-    (sparse_gpr.py:108-195 against oracle.VFEOracle and its autograd)."""
+    (sparse_gpr.py:108-195): 8 smooth-kind cases against oracle.VFEOracle and its autograd, then 4 Exp cases with inducing
+    points on training rows against tests/_xref.DirectVFE."""
     print(_run("fuzz_vfe.py", 8, 5, 600))
 
 
