@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """Switching a gptorch script to gptorch_amd: the workflow of the reference's 1-D regression example
-(GPR over a sum kernel -- or a sparse VFE model --, scipy L-BFGS-B, predictions and posterior samples) on an MI355X.  Only the
+(GPR over a sum kernel -- or a sparse VFE / minibatch SVGP model --, scipy L-BFGS-B or Adam, predictions and posterior samples) on an MI355X.  Only the
 import lines differ from a gptorch script, plus ONE line: `settings.auto_device = True` (or GPTORCH_AMD_AUTO_DEVICE=1 in the
 environment) lets the CPU-constructed model place itself on the GPU at its first call, like the reference's example, which
 never calls .cuda() (examples/regression_1d.py:89-95).  Without it `model.cuda()` is mandatory: there is no CPU path.
 
-    python examples/fit_1d_gp.py [--sparse] [--n 100] [--restarts 6]
+    python examples/fit_1d_gp.py [--sparse | --svgp] [--n 100] [--restarts 6]
 
 --restarts K (not in the reference, which fits one model per optimize() call): K exact-GP restarts with an Rbf kernel from
 different initial length scales, all K L-BFGS-B runs AT ONCE -- every round of function evaluations is one lock-step
@@ -22,7 +22,7 @@ import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))   # run from a checkout without installing
 
 from gptorch_amd import kernels, settings  # was: from gptorch import kernels
-from gptorch_amd.models import GPR, VFE    # was: from gptorch.models.gpr import GPR / sparse_gpr import VFE
+from gptorch_amd.models import GPR, SVGP, VFE    # was: from gptorch.models.gpr import GPR / sparse_gpr import VFE, SVGP
 from gptorch_amd.models import multi_start_optimize
 
 
@@ -33,6 +33,7 @@ def target(x):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--sparse", action="store_true", help="variational sparse GP (VFE) instead of the exact one")
+    ap.add_argument("--svgp", action="store_true", help="minibatch sparse variational GP (SVGP), fitted with Adam")
     ap.add_argument("--n", type=int, default=100)
     ap.add_argument("--restarts", type=int, default=0, help="multi-start: this many Rbf restarts optimised in lock step")
     args = ap.parse_args()
@@ -42,10 +43,12 @@ def main():
 
     if args.sparse:      # K(Z) of a sum with rank-one terms on 20 points is singular to working precision: Matern52 here
         model = VFE(x, y, kernels.Matern52(1), num_inducing_points=20)
+    elif args.svgp:      # (regression_1d.py fits SVGP next to GPR and VFE)
+        model = SVGP(x, y, kernels.Matern52(1), num_inducing_points=20, batch_size=min(args.n, 50))
     else:
         model = GPR(x, y, kernels.Linear(1) + kernels.Rbf(1) + kernels.Constant(1))
     settings.auto_device = True          # opt-in: the model moves itself to the GPU at its first loss() / predict call
-    if args.restarts > 1 and not args.sparse:
+    if args.restarts > 1 and not (args.sparse or args.svgp):
         xs_, ys_ = torch.as_tensor(x).cuda(), torch.as_tensor(y).cuda()          # the restarts share the data on the device
         restarts = []
         for ell in np.geomspace(0.02, 2.0, args.restarts):
@@ -56,6 +59,8 @@ def main():
         best = int(np.argmin([r.fun for r in results]))
         print("multi-start: %d restarts in %.2f s, final losses %s -> restart %d" % (args.restarts, seconds, [round(float(r.fun), 3) for r in results], best))
         model = restarts[best]
+    elif args.svgp:      # a stochastic bound: a torch optimiser, one fresh minibatch per step
+        model.optimize(method="Adam", max_iter=500, learning_rate=0.02, verbose=False)
     else:
         model.optimize(method="L-BFGS-B", max_iter=100)
     print(model)

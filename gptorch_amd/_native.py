@@ -108,6 +108,10 @@ SIGNATURES = {
     "gpn_refine_resid_part_work_bytes": (c_int64, [c_int, c_int64]),
     "gpn_refine_resid_part": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                       c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p]),
+    "gpn_svgp_marginals": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int,
+                                   c_void_p, c_int64, c_void_p, c_void_p]),
+    "gpn_svgp_backward_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
     "gpn_refine_finish": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
 }
 class ExprTerm(ctypes.Structure):

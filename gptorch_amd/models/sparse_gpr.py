@@ -34,7 +34,8 @@ by construction; the sandwich loses definiteness by ~eps |Kuf|^2 / lambda_min(Ku
 config 5 (4096 inducing points, Kuu at the edge of the jitter ladder) chol(B) then fails on
 every rung.  Measured, not assumed (round 1).
 
-SVGP / FITC (sparse_gpr.py:76-90, 198-381) are out of scope.
+SVGP (sparse_gpr.py:198-381) follows VFE below: a minibatch bound over the same M-sized algebra with its own row kernels
+(csrc/svgp.hip).  FITC (sparse_gpr.py:76-90, an empty class in the reference) stays out of scope.
 """
 import math
 
@@ -536,3 +537,402 @@ class VFE(_InducingPointsGP):
             _ops.gemm_nt(T2, T2, ns, ns, kp, alpha=1.0, beta=1.0, C=cov)
             _ops.gemm_nt(T1, T1, ns, ns, kp, alpha=-1.0, beta=1.0, C=cov)
         return mean, cov
+
+
+# =====================================================================================================================
+# SVGP (sparse_gpr.py:198-381): minibatch bound, closed-form backward, prediction
+# =====================================================================================================================
+#
+# With L = chol K(Z), alpha = K(x_b, Z) L^-T [nb, M], w = L^-1 m [M, dy], beta = L^-1 S_L [M, M], Q = beta beta^T - I:
+#
+#     f_mean0 = alpha w        f_var_i = Kdiag_i + alpha_i Q alpha_i^T        (sparse_gpr.py:367-377)
+#     KL = dy/2 (|beta|_F^2 - M + 2 sum log L_ii - 2 sum log S_L,ii) + 1/2 |w|_F^2   (sum over output columns of the KL of
+#                                                                                     sparse_gpr.py:293-306; the prior mean cancels)
+#
+# Backward for upstream (g_mean [nb, dy], g_var [nb], g_kl), with h = alpha^T g_mean and G_Q = alpha^T diag(g_var) alpha
+# (accumulated over the row chunks) and U = L^-T:
+#
+#     G_alpha = g_mean w^T + 2 diag(g_var) alpha Q            dK(x_b, Z) = G_alpha U^T
+#     G_w = h + g_kl w                                        d/dm   = U G_w
+#     G_beta = 2 G_Q beta + g_kl dy beta                      d/dS_L = tril(U G_beta) - g_kl dy diag(1 / S_L,ii)
+#     E = w h^T + h w^T + g_kl w w^T + 2 (Q G_Q + G_Q Q) + 2 G_Q + g_kl dy Q           (symmetric)
+#     dK(Z, Z) = -1/2 U E U^T
+#
+# The last line is the sum of the three solves' pull-backs onto L (-L^-T [G_alpha^T alpha + G_w w^T + G_beta beta^T]) and of
+# the log-determinant term (g_kl dy diag(1 / L_ii)) taken through the Cholesky pull-back L^-T Phi(L^T G_L) L^-1: the bracket
+# is symmetric, so Phi (lower triangle, halved diagonal) and the symmetrisation collapse to the factor 1/2, and the
+# log-determinant's share Phi(L^T diag(1 / L_ii)) = I / 2 turns the "+ g_kl dy (Q + I)" of G_beta beta^T into "+ g_kl dy Q".
+# Checked against autograd through the reference's op chain by tests/golden/make_svgp_golden.py.
+GAUSSIAN_SHORTCUT = True   # likelihoods.Gaussian: the data term without the sqrt / square round trip of propagate_log's Normal
+
+
+class _SVGPNativeAsm(_NativeAsm):
+    def kdiag(self, xc):
+        return self.var, 0                                                 # Kdiag = variance for every row (kernels.py:174-179)
+
+    def grad_kdiag(self, xc, gv):
+        self.g_var += gv.sum()
+
+
+class _SVGPGenericAsm(_GenericAsm):
+    def kdiag(self, xc):
+        with torch.no_grad():
+            return self.kernel.Kdiag(xc).contiguous(), 1
+
+    def grad_kdiag(self, xc, gv):
+        with torch.enable_grad():
+            s = (self.kernel.Kdiag(xc) * gv).sum()
+            grads = torch.autograd.grad(s, self.params, allow_unused=True)
+        for acc, g in zip(self.g_params, grads):
+            if g is not None:
+                acc += g
+
+
+class _SVGPState:
+    """the M-sized state of one evaluation (+ the single chunk's alpha and T, kept for the backward)."""
+    __slots__ = ("f_uu", "betaT", "Q", "w", "kl", "saved", "nc")
+
+
+def _sum_log_diag(A, m):
+    out = torch.empty(3, dtype=torch.float64, device=A.device)
+    _ops._native.check(_ops._native.lib().gpn_lml_reduce(_ops._stream(A.device), _ops._ptr(A), m, 0, A.stride(0), _ops._ptr(out)),
+                       "gpn_lml_reduce")
+    return out[0]
+
+
+def _svgp_chunk_rows(n):
+    return min(_ops.round_up(n, _ops.LEAF), _ops.round_up(CHUNK_ROWS, _ops.LEAF))
+
+
+def _svgp_m_state(asm, Z, m_u, S_L):
+    """chol K(Z), beta^T, Q, w and the KL term."""
+    dev = Z.device
+    m, dy = m_u.shape
+    mp = _ops.round_up(m, 16)
+    lib = _ops._native.lib()
+    st = _SVGPState()
+    st.f_uu = f_uu = asm.factor_uu(Z)
+    ld = f_uu.ld
+    st.betaT = BT = _ops.padded_like_factor(f_uu, m)                       # beta^T = S_L^T L^-T
+    BT[:m, :m] = S_L.t()
+    f_uu.solve_right_lt(BT, m)
+    beta = _ops.zeros(BT.shape[0], ld, dev)
+    _ops._native.check(lib.gpn_transpose(_ops._stream(dev), _ops._ptr(BT), m, m, ld, _ops._ptr(beta), ld), "gpn_transpose")
+    st.Q = Q = _ops.zeros(BT.shape[0], ld, dev)
+    _ops.gemm_nt(beta, beta, m, m, mp, C=Q)                                # beta beta^T
+    bb = _ops.diag_sum(Q, m)                                               # |beta|_F^2 = tr(beta beta^T)
+    Q.diagonal()[:m].sub_(1.0)
+    WT = _ops.padded_like_factor(f_uu, dy)                                 # w^T = m^T L^-T
+    WT[:dy, :m] = m_u.t()
+    f_uu.solve_right_lt(WT, dy)
+    st.w = w = WT[:dy, :m].t().contiguous()                                # [m, dy]
+    S_c = _ops._c(S_L)
+    st.kl = 0.5 * dy * (bb - m + 2.0 * f_uu.lml_terms()[0] - 2.0 * _sum_log_diag(S_c, m)) + 0.5 * _ops.dot2d(w, w)
+    st.saved = None
+    return st
+
+
+def _svgp_alpha_T(asm, st, xc, Z, At, T):
+    """alpha = K(x_c, Z) L^-T into At, T = alpha Q into T."""
+    r, m = xc.shape[0], Z.shape[0]
+    asm.kuf(xc, Z, At, st.f_uu.ld)
+    st.f_uu.solve_right_lt(At, r)
+    _ops.gemm_nt(At, st.Q, r, m, _ops.round_up(m, 16), C=T)
+
+
+def _svgp_forward(asm, x, Z, m_u, S_L):
+    """-> (f_mean0 [n, dy], f_var [n], state): sparse_gpr.py:358-377 without the mean function, rows streamed in chunks."""
+    x = _ops._c(x)
+    dev = x.device
+    n, (m, dy) = x.shape[0], m_u.shape
+    lib = _ops._native.lib()
+    st = _svgp_m_state(asm, Z, m_u, S_L)
+    ld = st.f_uu.ld
+    st.nc = nc = _svgp_chunk_rows(n)
+    f_mean = torch.empty(n, dy, dtype=torch.float64, device=dev)
+    f_var = torch.empty(n, dtype=torch.float64, device=dev)
+    At, T = _ops.zeros(nc + 16, ld, dev), _ops.zeros(nc, ld, dev)
+    for c0, r in _chunks(n, nc):
+        if c0 > 0 and r < nc:                                              # ragged tail of a multi-chunk evaluation: stale rows -> 0
+            At.zero_()
+        xc = x[c0:c0 + r]
+        _svgp_alpha_T(asm, st, xc, Z, At, T)
+        kd, kds = asm.kdiag(xc)
+        _ops._native.check(lib.gpn_svgp_marginals(_ops._stream(dev), _ops._ptr(At), ld, _ops._ptr(T), ld, r, m, _ops._ptr(st.w), dy, dy,
+                                                  _ops._ptr(kd), kds, _ops._ptr(f_mean[c0:]), _ops._ptr(f_var[c0:])),
+                           "gpn_svgp_marginals")
+    if n <= nc:
+        st.saved = (At, T)                                                 # one chunk: the backward starts from these
+    return f_mean, f_var, st
+
+
+def _svgp_backward(asm, x, Z, S_L, st, g_mean, g_var, g_kl):
+    """-> (d/d induced_output_mean [m, dy], d/d S_L [m, m]); kernel / inducing-point gradients are left in `asm`."""
+    x = _ops._c(x)
+    dev = x.device
+    n, (m, dy) = x.shape[0], st.w.shape
+    mp, dyp = _ops.round_up(m, 16), _ops.round_up(dy, 16)
+    lib = _ops._native.lib()
+    f_uu, w, Q, BT = st.f_uu, st.w, st.Q, st.betaT
+    ld, nc = f_uu.ld, st.nc
+    U = _backward._upper_inverse(f_uu)                                     # L^-T
+    asm.begin(Z)
+    GQ = _ops.zeros(Q.shape[0], ld, dev)
+    h = _zeros(mp, dy, dev)
+    aT, gaT = _ops.zeros(mp, nc, dev), _ops.zeros(mp, nc, dev)
+    gmT = _zeros(dyp, nc, dev)
+    Gx = torch.empty(nc, ld, dtype=torch.float64, device=dev)
+    if st.saved is not None:
+        At, T = st.saved
+    else:
+        At, T = _ops.zeros(nc + 16, ld, dev), _ops.zeros(nc, ld, dev)
+    for c0, r in _chunks(n, nc):
+        xc = x[c0:c0 + r]
+        if st.saved is None:
+            if c0 > 0 and r < nc:
+                At.zero_(), gmT.zero_()
+            _svgp_alpha_T(asm, st, xc, Z, At, T)
+        gv, gm = _ops._c(g_var[c0:c0 + r]), _ops._c(g_mean[c0:c0 + r])
+        _ops._native.check(lib.gpn_svgp_backward_rows(_ops._stream(dev), _ops._ptr(At), ld, _ops._ptr(T), ld, r, m, _ops._ptr(w), dy, dy,
+                                                      _ops._ptr(gv), _ops._ptr(gm), _ops._ptr(aT), _ops._ptr(gaT), nc),
+                           "gpn_svgp_backward_rows")
+        gmT[:dy, :r] = gm.t()
+        kp = _ops.round_up(r, 16)
+        first = 0.0 if c0 == 0 else 1.0
+        _ops.gemm_nt(gaT, aT, m, m, kp, beta=first, C=GQ)                  # G_Q += alpha^T diag(g_var) alpha
+        _ops.gemm_nt(aT, gmT, m, dy, kp, beta=first, C=h)                  # h += alpha^T g_mean
+        _ops.gemm_nt(T, U, r, m, mp, C=Gx, tri=_ops.TRI_B_UPPER)           # dK(x_c, Z) = G_alpha L^-1
+        asm.grad_uf(xc, Z, Gx[:r, :m])
+        asm.grad_kdiag(xc, gv)
+    st.saved = None
+
+    # M-sized part
+    h = h[:m]
+    GQs = torch.zeros_like(GQ)
+    GQs[:m, :m] = 0.5 * (GQ[:m, :m] + GQ[:m, :m].t())                      # (symmetric up to the rounding of the two operands)
+    QG = _ops.gemm_nt(Q, GQs, m, m, mp)                                    # Q G_Q
+    kd = g_kl * dy
+    E = _ops.matmul_nt(w, h)
+    E = E + E.t() + g_kl * _ops.matmul_nt(w, w) + 2.0 * (QG + QG.t()) + 2.0 * GQs[:m, :m] + kd * Q[:m, :m]
+    W = torch.zeros_like(U)
+    W[:m, :m] = -0.5 * E
+    asm.grad_uu(Z, _sandwich(U, W, m)[:m, :m])                             # dK(Z, Z) = -1/2 U E U^T
+    GbT = torch.zeros_like(BT)
+    _ops.gemm_nt(BT, GQs, m, m, mp, alpha=2.0, C=GbT)                      # G_beta^T = 2 beta^T G_Q + g_kl dy beta^T
+    GbT[:m, :m] += kd * BT[:m, :m]
+    g_S = torch.tril(_ops.gemm_nt(U, GbT, m, m, mp, tri=_ops.TRI_A_UPPER))  # L^-T G_beta, lower triangle
+    g_S.diagonal().sub_(kd / S_L.diagonal())
+    GwT = _zeros(dyp, ld, dev)
+    GwT[:dy, :m] = (h + g_kl * w).t()
+    g_m = _ops.gemm_nt(U, GwT, m, dy, mp, tri=_ops.TRI_A_UPPER)            # L^-T G_w
+    return g_m, g_S
+
+
+def _grads_or_zero(g_mean, g_var, g_kl, f_mean, f_var):
+    g_mean = torch.zeros_like(f_mean) if g_mean is None else g_mean
+    g_var = torch.zeros_like(f_var) if g_var is None else g_var
+    g_kl = torch.zeros((), dtype=torch.float64, device=f_var.device) if g_kl is None else g_kl
+    return g_mean, g_var, g_kl
+
+
+class _SVGPNode(torch.autograd.Function):
+    """q(f)'s marginals on a batch and KL(q(u) || p(u)) as one autograd node over (variance, length_scales, Z,
+    induced_output_mean, S_L): -> (f_mean0 [nb, dy], f_var [nb], KL)."""
+
+    @staticmethod
+    def forward(ctx, variance, length_scales, Z, m_u, S_L, kind, x):
+        asm = _SVGPNativeAsm(kind, variance.detach(), length_scales.detach())
+        f_mean, f_var, st = _svgp_forward(asm, x, Z.detach(), m_u.detach(), S_L.detach())
+        ctx.asm, ctx.x, ctx.st = asm, x, st
+        ctx.save_for_backward(length_scales, Z, S_L, f_mean, f_var)
+        return f_mean, f_var, st.kl
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_mean, g_var, g_kl):
+        length_scales, Z, S_L, f_mean, f_var = ctx.saved_tensors
+        g_mean, g_var, g_kl = _grads_or_zero(g_mean, g_var, g_kl, f_mean, f_var)
+        g_m, g_S = _svgp_backward(ctx.asm, ctx.x, Z.detach(), S_L.detach(), ctx.st, g_mean, g_var, g_kl)
+        g_v, g_ls, g_Z = ctx.asm.tensors()
+        return g_v, g_ls.reshape(length_scales.shape), g_Z, g_m, g_S, None, None
+
+
+class _SVGPNodeGeneric(torch.autograd.Function):
+    """The same node for any kernel object: over (Z, induced_output_mean, S_L, *raw kernel parameters)."""
+
+    @staticmethod
+    def forward(ctx, Z, m_u, S_L, kernel, x, *params):
+        asm = _SVGPGenericAsm(kernel, list(params))
+        f_mean, f_var, st = _svgp_forward(asm, x, Z.detach(), m_u.detach(), S_L.detach())
+        ctx.asm, ctx.x, ctx.st = asm, x, st
+        ctx.save_for_backward(Z, S_L, f_mean, f_var)
+        return f_mean, f_var, st.kl
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_mean, g_var, g_kl):
+        Z, S_L, f_mean, f_var = ctx.saved_tensors
+        g_mean, g_var, g_kl = _grads_or_zero(g_mean, g_var, g_kl, f_mean, f_var)
+        g_m, g_S = _svgp_backward(ctx.asm, ctx.x, Z.detach(), S_L.detach(), ctx.st, g_mean, g_var, g_kl)
+        *g_params, g_Z = ctx.asm.tensors()
+        return (g_Z, g_m, g_S, None, None) + tuple(g_params)
+
+
+# ---- host-side initialisation (sparse_gpr.py:310-335): runs once on <= 100 points, before the model moves to the GPU ------
+def _host_K(kernel, X, X2=None):
+    """K(X, X2) of the shell's kernel classes in plain fp64 torch on the host (the kernels' own `K` is native-only)."""
+    from .. import kernels
+    v = lambda p: p.transform().detach().cpu()
+    other = X if X2 is None else X2
+    if isinstance(kernel, kernels.Sum):
+        return _host_K(kernel.kern1, X, X2) + _host_K(kernel.kern2, X, X2)
+    if isinstance(kernel, kernels.Product):
+        return _host_K(kernel.kern1, X, X2) * _host_K(kernel.kern2, X, X2)
+    if isinstance(kernel, kernels.Linear):
+        return (X * v(kernel.variance)) @ other.t()
+    if isinstance(kernel, kernels.White):
+        return v(kernel.variance).expand(X.shape[0]).diag() if X2 is None else torch.zeros(X.shape[0], other.shape[0], dtype=X.dtype)
+    if isinstance(kernel, kernels.Constant):
+        return v(kernel.variance).expand(X.shape[0], other.shape[0]).clone()
+    if isinstance(kernel, kernels.Stationary) and kernel._kind is not None:
+        ls, var = v(kernel.length_scales), v(kernel.variance)
+        diff = (X / ls)[:, None, :] - (other / ls)[None, :, :]
+        r2 = (diff * diff).sum(-1)
+        kind = kernel._kind
+        if kind == "Rbf":
+            return var * torch.exp(-0.5 * r2)
+        r = torch.sqrt(torch.clamp(r2, min=1e-40))
+        if kind == "Matern52":
+            return var * (1.0 + math.sqrt(5.0) * r + 5.0 / 3.0 * r2) * torch.exp(-math.sqrt(5.0) * r)
+        if kind == "Matern32":
+            return var * (1.0 + math.sqrt(3.0) * r) * torch.exp(-math.sqrt(3.0) * r)
+        if kind == "Exp":
+            return var * torch.exp(-r)
+        if kind == "Periodic":
+            return var * torch.cos(r)
+    return kernel.K(X, X2).detach()                                        # a user's kernel: whatever its K does on the host
+
+
+def _host_cholesky(A):
+    """functions.cholesky on the host: plain try, then the jitter ladder of functions.py:20-43."""
+    out = []
+
+    def attempt(jitter):
+        Aj = A if jitter is None else A + jitter * torch.eye(A.shape[0], dtype=A.dtype)
+        L, info = torch.linalg.cholesky_ex(Aj)
+        out[:] = [L]
+        return int(info.item())
+    _ops._ladder(attempt)
+    return out[0]
+
+
+class SVGP(_InducingPointsGP):
+    """Sparse variational GP (Hensman et al. 2013 / 2015), sparse_gpr.py:219-381: q(u) = N(induced_output_mean + m(Z),
+    S_L S_L^T) over the induced outputs, minibatches of `batch_size` rows per evaluation of the bound."""
+
+    def __init__(self, x, y, kernel, num_inducing_points=None, inducing_points=None, mean_function=None, likelihood=None,
+                 batch_size=None):
+        from .. import likelihoods
+        super().__init__(x, y, kernel, num_inducing_points=num_inducing_points, inducing_points=inducing_points,
+                         mean_function=mean_function,
+                         likelihood=likelihood if likelihood is not None else likelihoods.Gaussian())   # sparse_gpr.py:238
+        self.batch_size = batch_size
+        # (induced_output_mean does NOT include the mean function's contribution, sparse_gpr.py:257-261)
+        self.induced_output_mean, self.induced_output_chol_cov = self._init_posterior()
+
+    def _init_posterior(self):
+        """sparse_gpr.py:310-335: the posterior at Z of an exact GP on <= 100 random points (one np.random.permutation draw)."""
+        from .. import likelihoods
+        from torch.distributions.transforms import LowerCholeskyTransform
+        i = np.random.permutation(self.num_data)[0: min(self.num_data, 100)]
+        with torch.no_grad():
+            x, y = self.X[i].detach().cpu(), self.Y[i].detach().cpu()
+            Z = self.Z.detach().cpu()
+            if isinstance(self.likelihood, likelihoods.Gaussian):
+                s2 = self.likelihood.variance.transform().detach().cpu()
+            else:
+                s2 = torch.tensor([0.01 * y.numpy().var()], dtype=torch.float64)
+            mean = lambda t: self.mean_function(t).detach().cpu()
+            L = _host_cholesky(_host_K(self.kernel, x) + s2.expand(x.shape[0]).diag())                 # gpr.py:104
+            A = torch.linalg.solve_triangular(L, _host_K(self.kernel, x, Z), upper=False)
+            V = torch.linalg.solve_triangular(L, y - mean(x), upper=False)
+            m_u = A.t() @ V                                                                           # gpr.py:107 minus m(Z) again
+            cov = _host_K(self.kernel, Z) - A.t() @ A
+            chol_cov = _host_cholesky(cov)
+        dev = self.Z.device
+        return Param(m_u.to(dev)), Param(chol_cov.to(dev), transform=LowerCholeskyTransform())
+
+    def _native_kernel(self):
+        from .. import kernels
+        k = self.kernel
+        return k if isinstance(k, kernels.Stationary) and k._kind is not None else None
+
+    def _marginals(self, x):
+        """-> (f_mean0 [n, dy] without the mean function, f_var [n], KL) through the native node."""
+        k = self._native_kernel()
+        S_L = self.induced_output_chol_cov.transform()
+        if k is not None:
+            return _SVGPNode.apply(k.variance.transform(), k.length_scales.transform(), self.Z, self.induced_output_mean, S_L,
+                                   k._kind, x)
+        params = [p for p in self.kernel.parameters() if p.requires_grad]
+        return _SVGPNodeGeneric.apply(self.Z, self.induced_output_mean, S_L, self.kernel, x, *params)
+
+    def _data_term(self, f_mean, f_var, y):
+        """sum over output columns of likelihood.propagate_log(N(f_mean_j, f_var), y_j), sparse_gpr.py:276-283."""
+        from .. import likelihoods
+        lik = self.likelihood
+        if GAUSSIAN_SHORTCUT and type(lik) is likelihoods.Gaussian:
+            # likelihoods.py:125-144 summed over the columns, f_var used as it is
+            s2 = lik.variance.transform()
+            n = y.nelement()
+            return (-0.5 * (n * (math.log(2.0 * math.pi) + torch.log(s2))
+                            + (torch.sum((y - f_mean) ** 2) + y.shape[1] * f_var.sum()) / s2)).reshape(())
+        sd = torch.sqrt(f_var)
+        return torch.stack([lik.propagate_log(torch.distributions.Normal(f_mean[:, j], sd), y[:, j]).reshape(())
+                            for j in range(y.shape[1])]).sum()
+
+    def log_likelihood(self, x=None, y=None):
+        """variational bound, sparse_gpr.py:198-216 (minibatch rule) and 263-308 (0-dim tensor)."""
+        if x is not None:
+            if y is None:                                                    # (the reference: `assert y is not None`)
+                raise ValueError("y is required when x is given")
+        elif self.batch_size is not None:
+            i = np.random.permutation(self.num_data)[: self.batch_size]     # the reference's host draw, one per evaluation
+            x, y = self.X[i, :], self.Y[i, :]
+        else:
+            x, y = self.X, self.Y
+        if not x.shape[0] == y.shape[0]:
+            raise ValueError("X and Y must have same # data.")
+        f_mean0, f_var, kl = self._marginals(x)
+        f_mean = f_mean0 + self.mean_function(x)
+        return self._data_term(f_mean, f_var, y) * (self.num_data / x.shape[0]) - kl
+
+    def _predict(self, x_new, diag=True, chol_kuu=None, **kwargs):
+        """sparse_gpr.py:337-381; chol_kuu is accepted for the reference's signature (the factor is native here)."""
+        with torch.no_grad():
+            Z, m_u = self.Z.detach(), self.induced_output_mean.detach()
+            S_L = self.induced_output_chol_cov.transform().detach()
+            k = self._native_kernel()
+            asm = _SVGPNativeAsm(k._kind, k.variance.transform().detach(), k.length_scales.transform().detach()) \
+                if k is not None else _SVGPGenericAsm(self.kernel, [])
+            mu_x = self.mean_function(x_new)
+            if diag:
+                f_mean0, f_var, _ = _svgp_forward(asm, x_new, Z, m_u, S_L)
+                f_mean = f_mean0 + mu_x
+                return f_mean, f_var[:, None].expand_as(f_mean)
+            st = _svgp_m_state(asm, Z, m_u, S_L)
+            f_uu = st.f_uu
+            ns, m, dy = x_new.shape[0], Z.shape[0], m_u.shape[1]
+            kp = _ops.round_up(m, 16)
+            At = _ops.padded_like_factor(f_uu, ns)
+            asm.kuf(_ops._c(x_new), Z, At, f_uu.ld)
+            f_uu.solve_right_lt(At, ns)                                                       # alpha
+            Gm = _ops.padded_like_factor(f_uu, ns)
+            _ops.gemm_nt(At, st.betaT, ns, m, kp, C=Gm)                                       # gamma = alpha beta
+            wT = _zeros(_ops.round_up(dy, 16), f_uu.ld, x_new.device)
+            wT[:dy, :m] = st.w.t()
+            f_mean = _ops.gemm_nt(At, wT, ns, dy, kp) + mu_x
+            cov = self.kernel.K(x_new).clone()
+            _ops.gemm_nt(Gm, Gm, ns, ns, kp, alpha=1.0, beta=1.0, C=cov)
+            _ops.gemm_nt(At, At, ns, ns, kp, alpha=-1.0, beta=1.0, C=cov)
+        return f_mean, cov

@@ -650,6 +650,26 @@ int gpn_dot2d_batched(void* stream, const double* x, int64_t ldx, int64_t sx, co
 int gpn_row_sumsq(void* stream, const double* A, int64_t rows, int64_t cols, int64_t lda,
                   double* out);
 
+/* ---- SVGP (sparse_gpr.py:198-381): the row kernels around the contractions --------------------------------------------
+ * With alpha = K(x_b, Z) L^-T [rows, m] (lda), T = alpha Q [rows, m] (ldt; Q = beta beta^T - I, beta = L^-1 S_L) and
+ * w = L^-1 induced_output_mean [m, dy] (ldw), all row-major with EVEN leading dimensions and 16-byte aligned bases
+ * (GPN_E_ALIGN otherwise):
+ *   f_var[i] = kdiag[i * kdiag_stride] + sum_j alpha_ij T_ij   (sparse_gpr.py:372-377; kdiag_stride 0: one value for all rows)
+ *   f_mean[i, c] = sum_j alpha_ij w_jc                          (sparse_gpr.py:367, without the mean function)
+ * in ONE pass over alpha and T: one wavefront-level reduction per row in a fixed order (the same inputs give the same bits;
+ * no atomics).  f_mean [rows, dy] contiguous, f_var [rows]. */
+int gpn_svgp_marginals(void* stream, const double* alpha, int64_t lda, const double* T, int64_t ldt, int64_t rows,
+                       int64_t m, const double* w, int64_t ldw, int dy, const double* kdiag, int64_t kdiag_stride,
+                       double* f_mean, double* f_var);
+/* The backward's pass over the same rows, for upstream gradients g_var [rows] and g_mean [rows, dy] (contiguous):
+ *   T <- G_alpha = 2 g_var_i T_i + g_mean_i w^T                 (in place)
+ *   alphaT [m, ldo] <- alpha^T,   galphaT [m, ldo] <- (diag(g_var) alpha)^T
+ * -- the NT operands of alpha^T diag(g_var) alpha and alpha^T g_mean -- transposed through LDS; their columns
+ * rows .. round_up(rows, 16) - 1 are written as zeros (the contractions' K padding), so ldo >= round_up(rows, 16), ldo even. */
+int gpn_svgp_backward_rows(void* stream, const double* alpha, int64_t lda, double* T, int64_t ldt, int64_t rows,
+                           int64_t m, const double* w, int64_t ldw, int dy, const double* g_var, const double* g_mean,
+                           double* alphaT, double* galphaT, int64_t ldo);
+
 
 /* ---- optional launch profiler (bench.py's roofline legs) ---------------------- */
 /* While enabled, every contraction / assembly / gradient-sweep / leaf launch of this library is bracketed by two HIP events
