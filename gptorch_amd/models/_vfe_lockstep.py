@@ -22,7 +22,7 @@ factor that succeeds is copied into its slot -- the same assembly + factorisatio
 
 Scope: native stationary kinds, the single-chunk regime (N below 32768 rows: no split-K accumulators, no chunk pipelines),
 right-solves by recursion (M < BLOCKED_SOLVE_MIN_M or N < 4 M).  Anything else -- config 5's N = 10^6 / M = 4096 fills the
-chip by itself -- stays sequential (gptorch_amd/models/gpr.py:_vfe_groups decides).
+chip by itself -- stays sequential (gptorch_amd/models/_lockstep.py:_vfe_groups decides).
 """
 import math
 

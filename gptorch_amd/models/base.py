@@ -5,6 +5,7 @@ native hot path; no dense arithmetic happens here).
 """
 import os
 from time import time
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -50,6 +51,15 @@ _SCIPY_METHODS = ["CG", "BFGS", "Newton-CG", "Nelder-Mead", "Powell", "L-BFGS-B"
 
 
 FOREACH_ON_GPU = os.environ.get("GPTORCH_AMD_FOREACH", "1") != "0"     # _make_optimizer: multi-tensor optimiser kernels for GPU parameters
+
+
+class _PredictCache(NamedTuple):
+    """what a model keeps between predictions (GPModel._cached_state); the field order is read by index elsewhere"""
+    key: tuple              # (x._version, x.shape, Y._version, tag)
+    state: object           # GPR: the factor of Kyy with L^-1 (y - m) riding along; VFE: the M-sized state of the bound
+    params: torch.Tensor    # every parameter's raw value at the time, concatenated
+    x: torch.Tensor         # the tensors the state was built from, HELD (see _cached_state)
+    y: torch.Tensor
 
 
 class GPModel(Model):
@@ -187,72 +197,62 @@ class GPModel(Model):
             return False
         return True
 
-    def _optimize_captured(self, method, max_iter, verbose, learning_rate):
-        """see optimize(capture=True).  Numerics: the optimiser is built with capturable=True and its step counters in fp64
-        (torch creates them in the DEFAULT dtype, fp32, which would round the bias corrections to 1e-7): the trajectory
-        agrees with the ordinary loop's to rounding (device pow instead of the host's for beta ** step), not bit for bit.
+    def _captured_loop(self, trainable, make_optimizer, step, dev_losses, max_iter):
+        """max_iter optimiser iterations as replays of ONE hipGraph, for optimize(capture=True) and the stacked groups of
+        multi_start_optimize(capture=True).  trainable: the tensors the optimiser steps; make_optimizer(): builds it;
+        step(optimizer, idx): one iteration -- zero_grad(set_to_none=True), loss, backward, optimizer.step(), the loss stored in row
+        idx of dev_losses ([max_iter] for one model, [max_iter, B] for a group) unless idx is None -- and returns the loss.
+        Returns the optimiser.
+        Numerics: the optimiser is built with capturable=True and its step counters in fp64 (torch creates them in the DEFAULT
+        dtype, fp32, which would round the bias corrections to 1e-7): the trajectory agrees with the ordinary loop's to rounding
+        (device pow instead of the host's for beta ** step), not bit for bit.  CAPTURE_WARMUP eager steps run on a side stream,
+        then step(optimizer, None) is captured with the loss row addressed by a device-side counter.
         A replay whose factorisation reports info != 0 cannot climb the jitter ladder inside the graph: the flag is read every
         CAPTURE_CHUNK replays, and a chunk that saw one is rolled back (parameters, optimiser state) and repeated eagerly."""
         import inspect
         from .. import _ops
-        dev = self.X.device
-        parameters = [p for p in self.parameters() if p.requires_grad]
-        if learning_rate is None:
-            learning_rate = _TORCH_DEFAULT_LR[method]
+        dev = dev_losses.device
         prev_dtype = torch.get_default_dtype()
         torch.set_default_dtype(torch.float64)
         try:
-            self.optimizer = self._make_optimizer(method, parameters, learning_rate)
-            if "capturable" in inspect.signature(type(self.optimizer).__init__).parameters:
-                for g in self.optimizer.param_groups:
+            optimizer = make_optimizer()
+            if "capturable" in inspect.signature(type(optimizer).__init__).parameters:
+                for g in optimizer.param_groups:
                     g["capturable"] = True
-            losses_dev = torch.zeros(max(1, max_iter), dtype=torch.float64, device=dev)
             counter = torch.zeros(1, dtype=torch.long, device=dev)
-            tic = time()
-            print("{}: Start optimizing via {}".format(self.__class__.__name__, method))
-
-            def eager_step(idx):
-                self.optimizer.zero_grad(set_to_none=True)
-                loss = self.loss()
-                loss.backward()
-                self.optimizer.step()
-                losses_dev[idx] = loss.detach().reshape(())
-
             done = 0
             side = torch.cuda.Stream(device=dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side):
                 while done < min(self.CAPTURE_WARMUP, max_iter):
-                    eager_step(done)
+                    step(optimizer, done)
                     done += 1
             torch.cuda.current_stream(dev).wait_stream(side)
             if done < max_iter:
                 counter.fill_(done)
-                self.optimizer.zero_grad(set_to_none=True)
+                optimizer.zero_grad(set_to_none=True)
                 deferred = _ops.DeferredInfo(dev)
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph), deferred:
-                    loss = self.loss()
-                    loss.backward()
-                    self.optimizer.step()
-                    losses_dev.index_copy_(0, counter, loss.detach().reshape(1))
+                    loss = step(optimizer, None)
+                    dev_losses.index_copy_(0, counter, loss.detach().reshape(1, *dev_losses.shape[1:]))
                     counter.add_(1)
                 # (the capture itself executed nothing: iteration `done` is the first replay)
 
                 def snapshot():
-                    return ([p.detach().clone() for p in parameters],
-                            [{k: (v.clone() if torch.is_tensor(v) else v) for k, v in self.optimizer.state[p].items()} for p in parameters])
+                    return ([p.detach().clone() for p in trainable],
+                            [{k: (v.clone() if torch.is_tensor(v) else v) for k, v in optimizer.state[p].items()} for p in trainable])
 
                 def restore(snap):
                     with torch.no_grad():
-                        for p, v in zip(parameters, snap[0]):
+                        for p, v in zip(trainable, snap[0]):
                             p.copy_(v)
-                        for p, st in zip(parameters, snap[1]):
+                        for p, st in zip(trainable, snap[1]):
                             for k, v in st.items():
                                 if torch.is_tensor(v):
-                                    self.optimizer.state[p][k].copy_(v)     # IN PLACE: the graph holds these addresses
+                                    optimizer.state[p][k].copy_(v)          # IN PLACE: the graph holds these addresses
                                 else:
-                                    self.optimizer.state[p][k] = v
+                                    optimizer.state[p][k] = v
 
                 while done < max_iter:
                     chunk = min(self.CAPTURE_CHUNK, max_iter - done)
@@ -260,15 +260,41 @@ class GPModel(Model):
                     deferred.flag.zero_()
                     for _ in range(chunk):
                         graph.replay()
-                    if int(deferred.flag.item()) != 0:            # ONE read-back per chunk
+                    if int(deferred.flag.item()) != 0:                      # ONE read-back per chunk
                         restore(snap)
                         for k in range(chunk):
-                            eager_step(done + k)
+                            step(optimizer, done + k)
                         counter.fill_(done + chunk)
                     done += chunk
-            losses = losses_dev[:max_iter].cpu().numpy().astype(np.float64)
         finally:
             torch.set_default_dtype(prev_dtype)
+        return optimizer
+
+    def _optimize_captured(self, method, max_iter, verbose, learning_rate):
+        """see optimize(capture=True); the capture itself is _captured_loop."""
+        dev = self.X.device
+        parameters = [p for p in self.parameters() if p.requires_grad]
+        if learning_rate is None:
+            learning_rate = _TORCH_DEFAULT_LR[method]
+        losses_dev = torch.zeros(max(1, max_iter), dtype=torch.float64, device=dev)
+        tic = time()
+        print("{}: Start optimizing via {}".format(self.__class__.__name__, method))
+
+        def step(optimizer, idx):
+            optimizer.zero_grad(set_to_none=True)
+            loss = self.loss()
+            loss.backward()
+            optimizer.step()
+            if idx is not None:
+                losses_dev[idx] = loss.detach().reshape(())
+            return loss
+
+        def make_optimizer():
+            self.optimizer = self._make_optimizer(method, parameters, learning_rate)
+            return self.optimizer
+
+        self._captured_loop(parameters, make_optimizer, step, losses_dev, max_iter)
+        losses = losses_dev[:max_iter].cpu().numpy().astype(np.float64)
         for idx in range(max_iter):
             if verbose or idx % 20 == 0:
                 print("Iter: %d\tLoss: %s" % (idx, losses[idx]))
@@ -282,6 +308,33 @@ class GPModel(Model):
         """scipy.optimize.minimize on the flat raw-parameter vector (base.py:298-320)."""
         return minimize(fun=self._loss_and_grad, x0=self._get_param_array(), method=method, jac=True, tol=tol,
                         callback=callback, options=dict(disp=disp, maxiter=maxiter))
+
+    def _cache_stamp(self, tag, x):
+        return ((x._version, tuple(x.shape), self.Y._version, tag),
+                torch.cat([p.detach().reshape(-1) for p in self.parameters()]))
+
+    def _seed_cached_state(self, tag, x, state):
+        """point the prediction cache at a state built elsewhere (batched_factorise) from x, Y and the present parameters"""
+        key, params = self._cache_stamp(tag, x)
+        self._predict_cache = _PredictCache(key, state, params, x, self.Y)
+        self._predict_calls = 0
+
+    def _cached_state(self, tag, x, build):
+        """What a prediction starts from (GPR: the factor, VFE: the state of the bound), kept between predictions; build() makes
+        it on a miss.  It depends on the inputs and on EVERY model parameter, mean function included.  Inputs: the cache HOLDS
+        the tensors it was built from and compares identity + version counter (large, never edited through .data) -- a held
+        tensor cannot be freed, so a temporary `x=` re-allocated at the same address with equal shape and version can never pass
+        for the cached one (round-4 review: the key used data_ptr()).  Parameters are compared by value on the device (edits
+        through `.data` do not bump a version counter): one concatenation + one torch.equal = a single host sync per prediction.
+        _predict_calls counts the lookups a state has served (GPR forms L^-1 after a few; it does the counting)."""
+        with torch.no_grad():
+            key, params = self._cache_stamp(tag, x)
+            c = getattr(self, "_predict_cache", None)
+            if c is None or c.key != key or c.x is not x or c.y is not self.Y or c.params.shape != params.shape \
+                    or not torch.equal(c.params, params):
+                self._predict_cache = _PredictCache(key, build(), params, x, self.Y)
+                self._predict_calls = 0
+        return self._predict_cache.state
 
     def _predict(self, input_new, diag=True):
         raise NotImplementedError()

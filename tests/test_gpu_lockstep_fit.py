@@ -287,7 +287,7 @@ def test_multi_start_falls_back_for_what_cannot_run_in_lock_step(device):
 def test_batch_buffers_are_bounded_and_releasable(device):
     """round-4 advice: the lock-step buffer cache is keyed by the full group key, evicts least recently used entries and
     can be released."""
-    from gptorch_amd.models import gpr as G
+    from gptorch_amd.models import _lockstep as G
     G.release_batch_buffers()
     for n in (256, 384, 512, 640, 768, 896):
         ms = _restarts(device, n, 2, [("Rbf", False, 1.0, 1.0, 0.05), ("Rbf", False, 0.8, 1.4, 0.05)])
@@ -491,7 +491,7 @@ def test_lockstep_composite_kernels_are_bit_identical_to_sequential(device, n, d
                 (lambda: kernels.Rbf(d) + kernels.White(d, variance=0.01), 0.05)]
     a = _composites(device, n, d, dy, builders)
     b = _composites(device, n, d, dy, builders)
-    from gptorch_amd.models import gpr as G
+    from gptorch_amd.models import _lockstep as G
     groups = G._expression_groups(a)
     assert sorted(len(g) for _, g, _ in groups) == [2, 3]
     out = batched_loss_and_grad(a)

@@ -62,7 +62,7 @@ def test_ragged_batch_is_bit_identical_to_each_models_own_evaluation(device, cas
 import contextlib
 import io
 
-from gptorch_amd.models import gpr as gpr_mod, multi_start_optimize
+from gptorch_amd.models import _lockstep as gpr_mod, multi_start_optimize
 
 
 def _gprs(sizes, d=3, kind=kernels.Matern52, seed=0, noise=0.05, ls=None):
@@ -93,7 +93,7 @@ def test_models_of_unequal_size_share_one_lockstep_evaluation(device):
     sizes = (1500, 1400, 1333, 1201, 1500 - 1)
     ms = _gprs(sizes)
     groups = gpr_mod._lockstep_groups(ms)
-    assert len(groups) == 1 and len(groups[0][0]) == 6 and groups[0][0][5] == sizes and groups[0][0][1][0] == 1500
+    assert len(groups) == 1 and groups[0][0].sizes is not None and groups[0][0][5] == sizes and groups[0][0][1][0] == 1500
     seq_ll = [m.log_likelihood().detach().clone() for m in ms]
     for a, b in zip(seq_ll, batched_log_likelihood(ms)):
         assert torch.equal(a.reshape(-1), b.reshape(-1))
@@ -112,7 +112,7 @@ def test_ragged_groups_next_to_equal_groups_and_outliers(device):
     ms = _gprs((1900,) * 8 + (1800, 1800, 1700, 1650, 1601, 600, 2100))
     groups = gpr_mod._lockstep_groups(ms)
     assert sorted(len(g) for _, g in groups) == [5, 8]
-    assert [k[5] for k, g in groups if len(k) > 5] == [(1800, 1800, 1700, 1650, 1601)]
+    assert [k[5] for k, g in groups if k.sizes is not None] == [(1800, 1800, 1700, 1650, 1601)]
     own = _own(ms)
     losses = batched_loss_and_grad(ms)
     for m, (l0, g0), l1 in zip(ms, own, losses):

@@ -13,7 +13,7 @@ import torch
 from tests._util import load_json, load_npz
 from gptorch_amd import _native, _ops, kernels, likelihoods, mean_functions, rng
 from gptorch_amd.models import GPR, VFE, batched_log_likelihood, batched_loss_and_grad, multi_start_optimize
-from gptorch_amd.models import _vfe_lockstep, gpr as gpr_mod
+from gptorch_amd.models import _vfe_lockstep, _lockstep as gpr_mod
 
 pytestmark = pytest.mark.gpu
 

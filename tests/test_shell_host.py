@@ -351,6 +351,23 @@ def test_bench_self_launch_reports_a_dead_child(tmp_path):
     assert d["value"] is None and d["n_gpus"] == 2 and d["scaling"] == "strong" and "without a result line" in d["error"]
 
 
+@pytest.mark.parametrize("first", ["gptorch_amd.models._lockstep", "gptorch_amd.models._multistart", "gptorch_amd.models.gpr"])
+def test_models_modules_import_in_any_order(first):
+    """the lock-step and multi-start modules use GPR / VFE and models/gpr.py re-exports two_lane_streams: whichever of them a fresh
+    interpreter imports first, the package's public names and gptorch_amd.models.gpr.two_lane_streams resolve."""
+    import os
+    import subprocess
+    import sys
+    names = ["GPModel", "GPR", "batched_factorise", "batched_log_likelihood", "batched_loss_and_grad", "multi_start_optimize",
+             "release_batch_buffers", "SVGP", "VFE", "DistGPR"]
+    code = ("import importlib; importlib.import_module(%r); import gptorch_amd.models as M, gptorch_amd.models.gpr as G; "
+            "assert callable(G.two_lane_streams); missing = [n for n in %r if not callable(getattr(M, n, None))]; "
+            "assert not missing, missing" % (first, names))
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+
+
 def _two_models(x, y):
     return [GPR(x, y, kernels.Rbf(2, ARD=True)), GPR(x, y, kernels.Rbf(2, variance=1.3, length_scales=0.8, ARD=True))]
 
@@ -400,7 +417,7 @@ def test_multi_start_scipy_is_interruptible(oracle_backed, monkeypatch):
     """an exception that is not an evaluation failure (KeyboardInterrupt) ends the search: it propagates to the caller, every
     restart's `minimize` unwinds through _MultiStartAborted and no thread is left waiting for an answer."""
     import threading
-    from gptorch_amd.models import gpr as gpr_mod
+    from gptorch_amd.models import _multistart as gpr_mod
     _, x, y = oracle_backed
     models = _two_models(x, y)
     real = gpr_mod.batched_loss_and_grad
@@ -428,7 +445,7 @@ def test_multi_start_scipy_round_does_not_wait_for_a_silent_restart(oracle_backe
     a lock held elsewhere for a while) does not stop the others from being served."""
     import threading
     import time
-    from gptorch_amd.models import gpr as gpr_mod
+    from gptorch_amd.models import _multistart as gpr_mod
     _, x, y = oracle_backed
     models = _two_models(x, y)
     monkeypatch.setattr(gpr_mod, "_MULTI_START_STALL_S", 0.2)

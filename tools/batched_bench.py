@@ -8,7 +8,7 @@ ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, ROOT)
 from gptorch_amd import kernels, likelihoods, rng  # noqa: E402
 from gptorch_amd.models import GPR, batched_log_likelihood  # noqa: E402
-from gptorch_amd.models.gpr import two_lane_streams  # noqa: E402
+from gptorch_amd.models._lockstep import two_lane_streams  # noqa: E402
 
 what = sys.argv[1] if len(sys.argv) > 1 else "c2"
 Bs = [int(v) for v in sys.argv[2:]] or [1, 2, 4, 8, 16]

@@ -91,7 +91,7 @@ for case in cases:
     if replays:
         print("    (%d factorisations of the %d models climbed the jitter ladder, together)" % (replays, B), flush=True)
     if "--parts" in sys.argv:
-        from gptorch_amd.models import gpr as gpr_mod
+        from gptorch_amd.models import _lockstep as gpr_mod
 
         def fwd():
             with torch.no_grad():
