@@ -112,6 +112,11 @@ SIGNATURES = {
                                    c_void_p, c_int64, c_void_p, c_void_p]),
     "gpn_svgp_backward_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
+    "gpn_fitc_forward_work_bytes": (c_int64, [c_int64]),
+    "gpn_fitc_forward_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int, c_void_p, c_int64, c_double,
+                                      c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "gpn_fitc_backward_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int64, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64]),
     "gpn_refine_finish": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
 }
 class ExprTerm(ctypes.Structure):

@@ -4,4 +4,5 @@ from .gpr import GPR  # noqa: F401
 from ._lockstep import batched_factorise, batched_log_likelihood, batched_loss_and_grad, release_batch_buffers  # noqa: F401
 from ._multistart import multi_start_optimize  # noqa: F401
 from .sparse_gpr import SVGP, VFE  # noqa: F401
+from ._fitc import FITC  # noqa: F401
 from .dist_gpr import DistGPR  # noqa: F401

@@ -35,7 +35,8 @@ config 5 (4096 inducing points, Kuu at the edge of the jitter ladder) chol(B) th
 every rung.  Measured, not assumed (round 1).
 
 SVGP (sparse_gpr.py:198-381) follows VFE below: a minibatch bound over the same M-sized algebra with its own row kernels
-(csrc/svgp.hip).  FITC (sparse_gpr.py:76-90, an empty class in the reference) stays out of scope.
+(csrc/svgp.hip).  FITC (sparse_gpr.py:76-90, an empty class in the reference) lives in models/_fitc.py: the same streamed pipeline
+(_stream_gram) with its own row kernels (csrc/fitc.hip) between the right-solve and the accumulation.
 """
 import math
 
@@ -116,6 +117,29 @@ def _zeros(rows, cols, device):
 def _chunks(n, nc):
     for c0 in range(0, n, nc):
         yield c0, min(nc, n - c0)
+
+
+def _chunk_rows(n):
+    """rows of x per streamed chunk of an n-row evaluation (forward and backward of VFE, SVGP and FITC alike)."""
+    return min(_ops.round_up(n, _ops.LEAF), _ops.round_up(CHUNK_ROWS, _ops.LEAF))
+
+
+def _blocked_solve(m, n):
+    """whether a chunk's right-solve goes through the inverted 1024 x 1024 diagonal blocks of L_uu (see _stream_gram)."""
+    return m >= BLOCKED_SOLVE_MIN_M and n >= 4 * m
+
+
+def _solve_chunk(f_uu, wb_uu, At, Xo, r):
+    """A_c^T = K(x_c, Z) L^-T for the r rows assembled in At -> the buffer that holds it: At itself (in place, the recursion down
+    to the leaf inverses), or Xo when wb_uu = _ops.block_inverses(f_uu) is given (_blocked_solve).  The ONE place the choice is
+    acted on: a backward that recomputes A_c^T (FITC) gets the forward's bits."""
+    if wb_uu is None:
+        return f_uu.solve_right_lt(At, r)
+    m = f_uu.n
+    _ops._native.check(_ops._native.lib().gpn_trsm_right_lt_blocked(_ops._stream(At.device), _ops._ptr(f_uu.A), m, f_uu.ld, _ops._ptr(wb_uu),
+                                                                    _ops._ptr(At), r, At.stride(0), _ops._ptr(Xo), Xo.stride(0)),
+                       "gpn_trsm_right_lt_blocked")
+    return Xo
 
 
 class _State:
@@ -218,19 +242,19 @@ class _GenericAsm:
         return self.g_params + [self.g_Z]
 
 
-def _vfe_forward(asm, x, err, Z, s2):
-    """streamed evaluation of sparse_gpr.py:126-137 -> _State."""
+def _stream_gram(asm, x, err, Z, f_uu, fB, scale, rows_hook=None):
+    """The N-sized part of a collapsed inducing-point likelihood, streamed over row chunks of x:
+    -> (AAT = scale * sum_c A_c A_c^T in a buffer shaped like fB.A (lower), Aerr = sum_c A_c err_c [round_up(M, 16), dy]) with
+    A_c^T = K(x_c, Z) L^-T.  rows_hook(buf, errT, ci, c0, r) (FITC): called on the chunk's stream between the right-solve and the
+    transpose with the solved chunk buf [r, M]; it may rescale buf's rows in place and writes the chunk's residual operand
+    errT [round_up(dy, 16), nc] itself (without a hook: err_c^T)."""
     dev = x.device
     n, dy = err.shape
     m = Z.shape[0]
-    st = _State()
-    st.n, st.s2 = n, s2
-    st.f_uu = f_uu = asm.factor_uu(Z)
-    fB = _ops.Factor(m, dy, dev)
-    st.AAT = AAT = torch.zeros_like(fB.A)
+    AAT = torch.zeros_like(fB.A)
     mp = _ops.round_up(m, 16)
     Aerr = _zeros(mp, dy, dev)
-    nc = min(_ops.round_up(n, _ops.LEAF), _ops.round_up(CHUNK_ROWS, _ops.LEAF))
+    nc = _chunk_rows(n)
     nchunks = (n + nc - 1) // nc
     # Two chunk pipelines on two streams: while one chunk's SYRK (whose 2080 tiles fill the
     # 1280 workgroup slots 1.6 times: a poor last round) accumulates, the next chunk's assembly,
@@ -245,7 +269,7 @@ def _vfe_forward(asm, x, err, Z, s2):
     # round 4: the chunk's right-solve through the inverted 1024 x 1024 diagonal blocks of L_uu (gpn_trsm_right_lt_blocked:
     # M / 1024 steps of two large contractions) instead of the recursion down to the 128-wide leaf inverses, whose K <= 256
     # levels ran at ~12 TFLOP/s (round-3 review: colpanel_kernel 19 % of C5's kernel time); one more chunk-sized buffer per lane
-    blocked = m >= BLOCKED_SOLVE_MIN_M and n >= 4 * m
+    blocked = _blocked_solve(m, n)
     wb_uu = _ops.block_inverses(f_uu) if blocked else None
     xbufs = [_zeros(nc + 16, f_uu.ld, dev) for _ in range(lanes)] if blocked else None
     # split-K partial accumulators (see below): only when M^2/2 has too few 128x128 tiles to fill the GPU
@@ -254,7 +278,9 @@ def _vfe_forward(asm, x, err, Z, s2):
     parts = torch.zeros(split, AAT.shape[0], AAT.shape[1], dtype=torch.float64, device=dev) if split > 1 else None
     aerr_parts = torch.zeros(split, mp, dy, dtype=torch.float64, device=dev) if split > 1 else None
     acc_done = None                                                        # event: AAT/Aerr updated through chunk c-1
-    W_uu = _ops.lower_inverse(f_uu) if (m >= INVERSE_MIN_M and n >= 4 * m) else None
+    # (the measured-and-off inverse form below produces A_c directly in the [M, rows] layout: there is no [rows, M] chunk for a row
+    # hook to work on, so a hooked evaluation -- FITC -- never takes it, whatever INVERSE_MIN_M says)
+    W_uu = _ops.lower_inverse(f_uu) if (rows_hook is None and m >= INVERSE_MIN_M and n >= 4 * m) else None
     for stq in streams[1:]:
         stq.wait_stream(cur)
     for ci, (c0, r) in enumerate(_chunks(n, nc)):
@@ -271,16 +297,13 @@ def _vfe_forward(asm, x, err, Z, s2):
                 for b0 in range(0, m, INVERSE_BLOCK):
                     rows = min(INVERSE_BLOCK, m - b0)
                     _ops.gemm_nt(W_uu[b0:], At, rows, r, _ops.round_up(b0 + rows, 16), C=A[b0:])
-            elif blocked:
-                Xo = xbufs[ci % lanes]
-                _ops._native.check(lib.gpn_trsm_right_lt_blocked(stream, _ops._ptr(f_uu.A), m, f_uu.ld, _ops._ptr(wb_uu), _ops._ptr(At), r,
-                                                                 At.stride(0), _ops._ptr(Xo), Xo.stride(0)), "gpn_trsm_right_lt_blocked")
-                _ops._native.check(lib.gpn_transpose(stream, _ops._ptr(Xo), r, m, Xo.stride(0), _ops._ptr(A), nc), "gpn_transpose")
             else:
-                f_uu.solve_right_lt(At, r)                                 # A_c^T = Kuf_c^T L^-T
-                _ops._native.check(lib.gpn_transpose(stream, _ops._ptr(At), r, m, At.stride(0), _ops._ptr(A), nc),
-                                   "gpn_transpose")
-            errT[:dy, :r] = err[c0:c0 + r].t()
+                S = _solve_chunk(f_uu, wb_uu, At, xbufs[ci % lanes] if blocked else None, r)   # A_c^T = Kuf_c^T L^-T
+                if rows_hook is not None:
+                    rows_hook(S, errT, ci, c0, r)
+                _ops._native.check(lib.gpn_transpose(stream, _ops._ptr(S), r, m, S.stride(0), _ops._ptr(A), nc), "gpn_transpose")
+            if rows_hook is None:
+                errT[:dy, :r] = err[c0:c0 + r].t()
             kp = _ops.round_up(r, 16)
             first = 0.0 if c0 == 0 else 1.0
             if acc_done is not None:
@@ -291,7 +314,7 @@ def _vfe_forward(asm, x, err, Z, s2):
                 # range is dealt over `split` partial accumulators in ONE launch (8 x 528 tiles =
                 # 8.25 rounds); the partials are summed once, after the last chunk
                 _ops.gemm_nt_batched(A, A, m, m, kp // split, split, kp // split, kp // split, parts,
-                                     alpha=1.0 / s2, beta=first, lower=True)
+                                     alpha=scale, beta=first, lower=True)
                 # A err likewise: a 4096 x 65536 matrix-vector product is 128 workgroups of 4096
                 # K-steps each as one skinny contraction (0.98 ms), 8x more of 8x shorter ones here
                 _ops.gemm_nt_batched(A, errT, m, dy, kp // split, split, kp // split, kp // split, aerr_parts, beta=first)
@@ -302,7 +325,7 @@ def _vfe_forward(asm, x, err, Z, s2):
                 tgt = parts[0] if split > 1 else AAT
                 for k0 in range(0, kp, ks):
                     kk = min(ks, kp - k0)
-                    _ops.gemm_nt(A[:, k0:], A[:, k0:], m, m, kk, alpha=1.0 / s2, beta=(first if k0 == 0 else 1.0), C=tgt, lower=True)
+                    _ops.gemm_nt(A[:, k0:], A[:, k0:], m, m, kk, alpha=scale, beta=(first if k0 == 0 else 1.0), C=tgt, lower=True)
                 _ops.gemm_nt(A, errT, m, dy, kp, beta=first, C=(aerr_parts[0] if split > 1 else Aerr))
             acc_done = torch.cuda.Event()
             acc_done.record(stq)
@@ -314,6 +337,30 @@ def _vfe_forward(asm, x, err, Z, s2):
         torch.sum(parts, dim=0, out=AAT)
         torch.sum(aerr_parts, dim=0, out=Aerr)
         del parts
+    return AAT, Aerr
+
+
+def _factor_B(fB, AAT, Aerr, m):
+    """B = AAT + I = LB LB^T in fB (jitter ladder of functions.py:20-43), (Aerr)^T riding along as the factor's extra rows."""
+    def attempt(jitter):
+        fB.A.copy_(AAT)
+        fB.A.diagonal()[:m].add_(1.0 if jitter is None else 1.0 + jitter)  # B = AAT + I
+        fB.pack_rhs(Aerr)
+        return fB.potrf()
+    _ops._ladder(attempt)
+
+
+def _vfe_forward(asm, x, err, Z, s2):
+    """streamed evaluation of sparse_gpr.py:126-137 -> _State."""
+    dev = x.device
+    n, dy = err.shape
+    m = Z.shape[0]
+    st = _State()
+    st.n, st.s2 = n, s2
+    st.f_uu = f_uu = asm.factor_uu(Z)
+    fB = _ops.Factor(m, dy, dev)
+    st.AAT, Aerr = _stream_gram(asm, x, err, Z, f_uu, fB, 1.0 / s2)
+    AAT = st.AAT
     # row shards: one all-reduce of the M-sized sums and of (N, |err|^2)
     scal = torch.tensor([float(n), 0.0, 0.0], dtype=torch.float64, device=dev)
     scal[1] = _ops.dot2d(err, err)
@@ -325,13 +372,7 @@ def _vfe_forward(asm, x, err, Z, s2):
     st.n_all, st.yy_all, st.trkff = int(round(scal[0].item())), scal[1], scal[2]
     st.Aerr = Aerr[:m]
     st.tr = _ops.diag_sum(AAT, m)
-
-    def attempt(jitter):
-        fB.A.copy_(AAT)
-        fB.A.diagonal()[:m].add_(1.0 if jitter is None else 1.0 + jitter)  # B = AAT + I
-        fB.pack_rhs(st.Aerr)
-        return fB.potrf()
-    _ops._ladder(attempt)
+    _factor_B(fB, AAT, st.Aerr, m)
     st.fB = fB
     st.terms = fB.lml_terms()            # [sum log LB_ii, || LB^-1 A err ||^2 = s2^2 |c|^2, ...]
     return st
@@ -386,7 +427,7 @@ def _vfe_backward(asm, x, err, Z, st):
     Bq = _zeros(mp, ldk, dev)
     Bq[:m, :m] = P[:m, :m]
     Bq[:m, mp:mp + p] = gt[:p, :m].t()
-    nc = min(_ops.round_up(n, _ops.LEAF), _ops.round_up(CHUNK_ROWS, _ops.LEAF))
+    nc = _chunk_rows(n)
     Kx = _zeros(nc + 16, ldk, dev)
     G = torch.empty(nc, mp, dtype=torch.float64, device=dev)
     for c0, r in _chunks(n, nc):
@@ -592,7 +633,7 @@ def _sum_log_diag(A, m):
 
 
 def _svgp_chunk_rows(n):
-    return min(_ops.round_up(n, _ops.LEAF), _ops.round_up(CHUNK_ROWS, _ops.LEAF))
+    return _chunk_rows(n)
 
 
 def _svgp_m_state(asm, Z, m_u, S_L):

@@ -670,6 +670,30 @@ int gpn_svgp_backward_rows(void* stream, const double* alpha, int64_t lda, doubl
                            int64_t m, const double* w, int64_t ldw, int dy, const double* g_var, const double* g_mean,
                            double* alphaT, double* galphaT, int64_t ldo);
 
+/* ---- FITC (Snelson & Ghahramani 2006; gptorch_amd/models/_fitc.py): the row kernels around the contractions ------------
+ * Forward rows of a chunk A_c^T = K(x_c, Z) L^-T [rows, m] (At, row-major, lda even, 16-byte aligned base; the buffer holds
+ * round_up(rows, 16) rows), err [rows, dy] contiguous, kdiag as for gpn_svgp_marginals, noise >= 0:
+ *   lambda[i] = kdiag[i * kdiag_stride] - sum_j At_ij^2 + noise
+ *   At_i <- At_i / sqrt(lambda_i)  (in place);   errT[k, i] <- err[i, k] / sqrt(lambda_i)   (errT [dy, ldo], ldo >= round_up(rows, 16))
+ *   out2[0] = sum_i log lambda_i,   out2[1] = sum_i |err_i|^2 / lambda_i
+ * in ONE pass over At (m <= 4096: a row stays in registers between its sum of squares and its scaling).  Rows
+ * rows .. round_up(rows, 16) - 1 of At and the same columns of errT (the K padding of the contractions that read them) are
+ * written as exact zeros.  Sums in a fixed order, no atomics: per-workgroup partial pairs in `work`
+ * (gpn_fitc_forward_work_bytes(rows) bytes), combined by a second single-workgroup launch. */
+int64_t gpn_fitc_forward_work_bytes(int64_t rows);
+int gpn_fitc_forward_rows(void* stream, double* At, int64_t lda, int64_t rows, int64_t m, const double* err, int dy,
+                          const double* kdiag, int64_t kdiag_stride, double noise, double* errT, int64_t ldo,
+                          double* lambda, double* work, double* out2);
+/* Backward rows: alpha = A_c^T as above (unscaled), T [rows, ldt] = alpha [B^-1 | beta] from ONE contraction -- alpha B^-1 in
+ * columns 0 .. m - 1, alpha beta in columns round_up(m, 16) .. + dy - 1 (ldt >= round_up(m, 16) + dy, even) --, beta [m, dy]
+ * (ldb), err [rows, dy] and lambda [rows] contiguous:
+ *   r_out[i, :] = (err_i - alpha_i beta) / lambda_i,   g_out[i] = |r_i|^2 - dy (1 / lambda_i - alpha_i . T_i / lambda_i^2)
+ *   T_i <- r_i beta^T - (dy / lambda_i) T_i - g_i alpha_i      (columns 0 .. m - 1, in place: the rows of dF/dA^T)
+ *   alphaT [m, ldo] <- alpha^T,   galphaT [m, ldo] <- (diag(g) alpha)^T     (as gpn_svgp_backward_rows: zero K padding) */
+int gpn_fitc_backward_rows(void* stream, const double* alpha, int64_t lda, double* T, int64_t ldt, int64_t rows, int64_t m,
+                           const double* beta, int64_t ldb, int dy, const double* err, const double* lambda, double* r_out,
+                           double* g_out, double* alphaT, double* galphaT, int64_t ldo);
+
 
 /* ---- optional launch profiler (bench.py's roofline legs) ---------------------- */
 /* While enabled, every contraction / assembly / gradient-sweep / leaf launch of this library is bracketed by two HIP events
