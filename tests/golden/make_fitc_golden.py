@@ -1,13 +1,16 @@
-"""Writes tests/golden/fitc_cases.json: the FITC golden cases.  Inputs come from gptorch_amd.rng (regenerated from the seeds by
+"""Writes tests/golden/fitc_cases.json: the FITC golden cases (and, with --wide, tests/golden/fitc_wide_case.json: one case with
+M > 1024, nothing else touched).  Inputs come from gptorch_amd.rng (regenerated from the seeds by
 tests/_fitc_oracle.case_inputs), expected values from the host oracle tests/_fitc_oracle.py -- the dense N x N form in fp64
 (loss, gradients by autograd) and in long double (loss, predictions), and the distance e64 between the two that the GPU
 tests' tolerances are derived from (tests/_xref.tol).  Asserts on the way that K(Z) is well conditioned (no jitter ladder) and
 that the closed-form backward of gptorch_amd/models/_fitc.py equals autograd through the dense form.
 
-    python -m tests.golden.make_fitc_golden
+    python -m tests.golden.make_fitc_golden            # fitc_cases.json
+    python -m tests.golden.make_fitc_golden --wide     # fitc_wide_case.json only (long double at N = 1400: about a minute)
 """
 import json
 import os
+import sys
 
 import numpy as np
 
@@ -28,6 +31,10 @@ CASES = [
 ]
 TRAJECTORY = dict(name="adam_130x40x9", n=130, m=40, d=3, dy=9, kernel=dict(kind="Matern52", variance=1.2, length_scales=[0.9, 1.1, 1.3], ARD=True),
                   noise=0.05, seed_x=111, seed_xs=112, steps=5, learning_rate=0.01)
+# M > 1024 (a file of its own, written by --wide only): the <32> instantiation of the FITC forward row kernel and 18 column tiles
+# of its backward; Z = the first 1100 rows of X, so lambda = noise on those rows
+WIDE = dict(name="matern32_1400x1100x2", n=1400, m=1100, d=4, dy=2, kernel=dict(kind="Matern32", variance=1.3, length_scales=1.1), noise=0.08,
+            seed_x=151, seed_xs=152)
 # what every case carries (tests/test_fitc_host.py checks the file against it)
 SCHEMA = ("name", "n", "m", "d", "dy", "kernel", "noise", "seed_x", "seed_xs", "cond_Kuu", "closed_form_err", "loss", "loss_ld", "e64",
           "grads", "mean_pred", "var_pred", "cov_pred")
@@ -68,14 +75,21 @@ def make_trajectory(t):
     return out
 
 
-def main():
-    doc = dict(schema=list(SCHEMA), cases=[make_case(c) for c in CASES], trajectory=make_trajectory(TRAJECTORY))
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "fitc_cases.json")
+def write(doc, name):
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), name)
     with open(path, "w") as f:
         json.dump(doc, f, indent=1)
         f.write("\n")
     print("wrote", path, os.path.getsize(path), "bytes")
 
 
+def main():
+    write(dict(schema=list(SCHEMA), cases=[make_case(c) for c in CASES], trajectory=make_trajectory(TRAJECTORY)), "fitc_cases.json")
+
+
+def main_wide():
+    write(dict(schema=list(SCHEMA), cases=[make_case(WIDE)]), "fitc_wide_case.json")
+
+
 if __name__ == "__main__":
-    main()
+    main_wide() if "--wide" in sys.argv[1:] else main()

@@ -13,6 +13,7 @@ from tests._util import load_json
 from tests.golden import make_fitc_golden as maker
 
 CASES = load_json("fitc_cases.json")
+WIDE = load_json("fitc_wide_case.json")
 IDS = [c["name"] for c in CASES["cases"]]
 
 
@@ -60,6 +61,24 @@ def test_golden_file_matches_the_makers_schema():
     assert any(c.get("mean") is not None for c in CASES["cases"])
     t = CASES["trajectory"]
     assert len(t["losses"]) == t["steps"] == 5 and all(a > b for a, b in zip(t["losses"], t["losses"][1:]))
+
+
+def test_wide_golden_file_matches_the_makers_schema():
+    """tests/golden/fitc_wide_case.json (make_fitc_golden.py --wide): one case with M > 1024, the schema of the others.  (Its
+    long-double evaluation at N = 1400 is the maker's and is not repeated here.)"""
+    assert WIDE["schema"] == list(maker.SCHEMA) and set(WIDE) == {"schema", "cases"} and len(WIDE["cases"]) == 1
+    case, spec = WIDE["cases"][0], maker.WIDE
+    assert set(maker.SCHEMA) <= set(case)
+    assert all(case[k] == v for k, v in spec.items())
+    assert case["m"] > 1024 and (case["n"], case["m"], case["d"], case["dy"], case["kernel"]["kind"]) == (1400, 1100, 4, 2, "Matern32")
+    assert case["cond_Kuu"] < 1e8 and case["closed_form_err"] < 1e-10 and case["noise"] >= 0.05
+    assert set(case["e64"]) == {"loss", "mean", "var", "cov", "grad"}
+    assert set(case["grads"]) == set(fo.model_names(case))
+    assert np.asarray(case["grads"]["Z"]).shape == (case["m"], case["d"])
+    assert np.asarray(case["mean_pred"]).shape == (16, case["dy"]) and np.asarray(case["cov_pred"]).shape == (16, 16)
+    assert np.isfinite(case["loss"]) and abs(xr.rel_err(case["loss"], case["loss_ld"]) - case["e64"]["loss"]) < 2.3e-16   # (loss_ld is stored rounded to fp64)
+    inp = fo.case_inputs(case)                                                 # Z is the first M rows of X: lambda = noise there
+    assert np.array_equal(inp["z"], inp["x"][:case["m"]])
 
 
 def test_closed_form_backward_equals_autograd(evaluated):

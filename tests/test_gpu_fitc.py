@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from gptorch_amd import kernels, likelihoods
+from gptorch_amd import kernels, likelihoods, rng
 from gptorch_amd.models import FITC, GPR, VFE, sparse_gpr
 from tests import _fitc_oracle as fo
 from tests import _xref as xr
@@ -23,6 +23,7 @@ pytestmark = pytest.mark.gpu
 CASES = load_json("fitc_cases.json")
 BY_NAME = {c["name"]: c for c in CASES["cases"]}
 BIG = BY_NAME["matern32_1000x200x3"]
+WIDE = load_json("fitc_wide_case.json")["cases"][0]                          # M = 1100 (make_fitc_golden.py --wide)
 
 
 def quiet():
@@ -78,6 +79,50 @@ def test_golden_cases(device, case):
     check_loss_and_grads(case, m)
     check_predictions(case, inp, m)
     assert m._state_for_predict(m.X) is m._state_for_predict(m.X)            # the state is kept between predictions
+
+
+def test_wide_golden_case(device):
+    """M = 1100 > 1024 (N = 1400, dy = 2, Z = the first 1100 rows of X: lambda = noise on those rows): the <32> instantiation of
+    the forward row kernel and 18 column tiles of the backward rows, against the dense N x N oracle like every golden case."""
+    assert WIDE["m"] > 1024 and WIDE["name"] == "matern32_1400x1100x2"
+    inp, m = cuda_model(WIDE)
+    check_loss_and_grads(WIDE, m)
+    check_predictions(WIDE, inp, m)
+
+
+def test_blocked_right_solve_matches_the_leaf_chain(device, monkeypatch):
+    """FITC's backward recomputes A_c^T through sparse_gpr._solve_chunk and must get the forward's bits, whichever right-solve that
+    is.  N = 4608, M = 1100 (the second 1024-block of L_uu is ragged), chunks of 2048 rows (two and a tail of 512): with the
+    blocked solve switched on (BLOCKED_SOLVE_MIN_M = 1024) the same likelihood and gradients as down the leaf chain -- the
+    tolerances of test_vfe_blocked_right_solve_matches_the_leaf_chain --, and the likelihood against the oracle's M-sized fp64
+    evaluation (1e-9 relative, as that test holds the VFE bound to its oracle)."""
+    n, mq, d = 4608, 1100, 3
+    x, y = rng.make_regression(n, d, 1, seed=41)
+    z = rng.normal(42, (mq, d)) * 2.0
+    res = {}
+    for name, thr in (("blocked", 1024), ("chain", 10 ** 9)):
+        monkeypatch.setattr(sparse_gpr, "BLOCKED_SOLVE_MIN_M", thr)
+        monkeypatch.setattr(sparse_gpr, "CHUNK_ROWS", 2048)
+        assert sparse_gpr._blocked_solve(mq, n) == (name == "blocked")
+        assert [r for _, r in sparse_gpr._chunks(n, sparse_gpr._chunk_rows(n))] == [2048, 2048, 512]
+        mod = FITC(x, y, kernels.Matern52(d, variance=1.2, length_scales=0.6), inducing_points=z.copy(), likelihood=likelihoods.Gaussian(variance=0.1))
+        mod.cuda()
+        loss = mod.loss()
+        loss.backward()
+        res[name] = (loss.item(), {k: p.grad.clone() for k, p in mod.named_parameters() if p.grad is not None})
+    (lb, gb), (lc, gc) = res["blocked"], res["chain"]
+    print("fitc blocked %.12f chain %.12f rel diff %.2e" % (lb, lc, abs(lb - lc) / abs(lc)))
+    assert abs(lb - lc) < 1e-10 * abs(lc), (lb, lc)
+    assert set(gb) == set(gc) and len(gc) >= 4
+    for k in gc:
+        diff = (gb[k] - gc[k]).abs().max().item()
+        print("   d/d%-28s max diff %.2e of max %.2e" % (k, diff, gc[k].abs().max().item()))
+        assert diff < 1e-7 * max(1.0, gc[k].abs().max().item()), k
+    o = fo.FITCOracle(x, y, z, dict(kind="Matern52", variance=1.2, length_scales=0.6), 0.1)
+    with torch.no_grad():
+        ref = o.woodbury_lml(*o._inputs()).item()
+    print("   oracle (Woodbury, fp64) %.12f rel diff %.2e" % (ref, abs(-lb - ref) / abs(ref)))
+    assert abs(-lb - ref) < 1e-9 * abs(ref), (lb, ref)
 
 
 @pytest.mark.parametrize("chunk", [None, 256], ids=["single_chunk", "multi_chunk"])
