@@ -30,7 +30,7 @@ import math
 
 import torch
 
-from .. import _backward, _ops
+from .. import _ops
 from . import sparse_gpr as _sg
 
 
@@ -71,6 +71,15 @@ def _lml(st, p):
     return -0.5 * p * st.n * math.log(2.0 * math.pi) - 0.5 * p * st.sums[0] - p * st.terms[0] - 0.5 * st.sums[1] + 0.5 * st.terms[1]
 
 
+def _fitc_evaluate(asm, x, err, Z, noise):
+    """-> (log p(Y), its state, the contiguous (x, err) the row kernels of forward and backward read) for the node
+    (sparse_gpr._CollapsedBound).  The noise is read on the host once per evaluation."""
+    s2 = float(noise.item())
+    x, err = _ops._c(x), _ops._c(err.detach())
+    st = _fitc_forward(asm, x, err, Z, s2)
+    return _lml(st, err.shape[1]), st, x, err
+
+
 def _fitc_backward(asm, x, err, Z, st):
     """-> (dF/d noise [1], dF/d err [N, dy]); the kernel / inducing-point gradients are left in `asm` (as sparse_gpr._vfe_backward)."""
     dev = x.device
@@ -80,10 +89,7 @@ def _fitc_backward(asm, x, err, Z, st):
     ld = f_uu.ld
     mp, pp = _ops.round_up(m, 16), _ops.round_up(p, 16)
     lib = _ops._native.lib()
-    U = _backward._upper_inverse(f_uu)                                     # L^-T
-    UB = _backward._upper_inverse(fB)                                      # LB^-T
-    Binv = _backward._kinv_lower(fB, UB)[:m, :m]
-    Binv = torch.tril(Binv) + torch.tril(Binv, -1).t()
+    U, UB, Binv = _sg._factor_inverses(f_uu, fB, m)
     bt = _ops.zeros(pp, ld, dev)                                           # beta^T = c^T LB^-1
     _ops.gemm_nt(fB.A[m:], UB, p, m, mp, C=bt, tri=_ops.TRI_B_UPPER)
     beta = bt[:p, :m].t().contiguous()                                     # [m, p]
@@ -118,7 +124,7 @@ def _fitc_backward(asm, x, err, Z, st):
         _ops.gemm_nt(gaT, aT, m, m, kp, beta=(0.0 if c0 == 0 else 1.0), C=AgA)   # A diag(g) A^T
         _ops.gemm_nt(T, U, r, m, mp, C=Gx, tri=_ops.TRI_B_UPPER)           # dF/dK(x_c, Z) = (dF/dA^T) L^-1
         asm.grad_uf(xc, Z, Gx[:r, :m])
-        asm.grad_kdiag(xc, 0.5 * g[c0:c0 + r])
+        asm.grad_kdiag(xc, 0.5 * g[c0:c0 + r])                             # dF/dKdiag_i = g_i / 2
 
     # K(Z, Z) part
     betap = _ops.zeros(mp, pp, dev)
@@ -132,112 +138,34 @@ def _fitc_backward(asm, x, err, Z, st):
     return (0.5 * g.sum()).reshape(1), r_all.neg_()
 
 
-class _FITCBound(torch.autograd.Function):
-    """The FITC marginal likelihood as one autograd node over (variance, length_scales, noise, Z, err)."""
-
-    @staticmethod
-    def forward(ctx, variance, length_scales, noise, Z, err, kind, x, holder):
-        s2 = float(noise.item())
-        asm = _sg._SVGPNativeAsm(kind, variance.detach(), length_scales.detach())
-        x, err = _ops._c(x), _ops._c(err.detach())
-        st = _fitc_forward(asm, x, err, Z.detach(), s2)
-        ctx.asm, ctx.x, ctx.err, ctx.st = asm, x, err, st
-        ctx.save_for_backward(length_scales, Z)
-        holder["state"] = st
-        return _lml(st, err.shape[1])
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        length_scales, Z = ctx.saved_tensors
-        g_noise, g_err = _fitc_backward(ctx.asm, ctx.x, ctx.err, Z.detach(), ctx.st)
-        g_var, g_ls, g_Z = ctx.asm.tensors()
-        g = grad_out
-        return (g * g_var, g * g_ls.reshape(length_scales.shape), g * g_noise, g * g_Z,
-                g * g_err if ctx.needs_input_grad[4] else None, None, None, None)
-
-
-class _FITCBoundGeneric(torch.autograd.Function):
-    """The same for any kernel object: node over (noise, Z, err, *raw kernel parameters); Kdiag(x_c) comes per chunk from the
-    kernel, and its gradient is pulled with the weights g_c / 2."""
-
-    @staticmethod
-    def forward(ctx, noise, Z, err, kernel, x, holder, *params):
-        s2 = float(noise.item())
-        asm = _sg._SVGPGenericAsm(kernel, list(params))
-        x, err = _ops._c(x), _ops._c(err.detach())
-        st = _fitc_forward(asm, x, err, Z.detach(), s2)
-        ctx.asm, ctx.x, ctx.err, ctx.st = asm, x, err, st
-        ctx.save_for_backward(Z)
-        holder["state"] = st
-        return _lml(st, err.shape[1])
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_out):
-        Z, = ctx.saved_tensors
-        g_noise, g_err = _fitc_backward(ctx.asm, ctx.x, ctx.err, Z.detach(), ctx.st)
-        *g_params, g_Z = ctx.asm.tensors()
-        g = grad_out
-        return (g * g_noise, g * g_Z, g * g_err if ctx.needs_input_grad[2] else None, None, None, None) + tuple(g * t for t in g_params)
-
-
 class FITC(_sg._InducingPointsGP):
     """Fully independent training conditional sparse GP regression.  Any kernel object (native stationary kinds through the
     fused assembly and the native sweeps, everything else through the kernel's own K / Kdiag and autograd), any mean function,
     a Gaussian likelihood.  Not a VFE: multi_start_optimize runs FITC restarts one after the other."""
 
-    def _native_kernel(self):
-        from .. import kernels
-        k = self.kernel
-        return k if isinstance(k, kernels.Stationary) and k._kind is not None else None
-
     def _bound(self, x, y):
         if _sg.SHARD_GROUP is not None:
             raise NotImplementedError("FITC does not shard rows over ranks (sparse_gpr.SHARD_GROUP is set)")
-        k = self._native_kernel()
         holder = {}
         s2 = self.likelihood.variance.transform()
         err = y - self.mean_function(x)
-        if k is not None:
-            lml = _FITCBound.apply(k.variance.transform(), k.length_scales.transform(), s2, self.Z, err, k._kind, x, holder)
-        else:
-            params = [p for p in self.kernel.parameters() if p.requires_grad]
-            lml = _FITCBoundGeneric.apply(s2, self.Z, err, self.kernel, x, holder, *params)
+        make_asm, tensors = self._kernel_adapter()
+        lml = _sg._CollapsedBound.apply(_fitc_evaluate, _fitc_backward, make_asm, holder, x, s2, self.Z, err, *tensors)
         return lml, holder["state"]
 
     def log_likelihood(self, x=None, y=None):
         """log p(Y) under the FITC prior (0-dim tensor)."""
-        x = x if x is not None else self.X
-        y = y if y is not None else self.Y
-        if not x.shape[0] == y.shape[0]:
-            raise ValueError("X and Y must have same # data.")
-        return self._bound(x, y)[0]
+        return self._bound(*self._data(x, y))[0]
 
     def _state_for_predict(self, x):
         """chol K(Z), chol B and c, kept between predictions (GPModel._cached_state, as VFE._state_for_predict)."""
         return self._cached_state("fitc", x, lambda: self._bound(x, self.Y)[1])
 
     def _predict(self, x_new, diag=True, x=None):
-        """VFE's predictive equations from FITC's state: mean = tmp2^T c + m(x*), var = Kdiag(x*) - |tmp1|^2 + |tmp2|^2 with
+        """The collapsed predictive equations (_InducingPointsGP._collapsed_predict) from FITC's state: mean = tmp2^T c + m(x*), var = Kdiag(x*) - |tmp1|^2 + |tmp2|^2 with
         tmp1^T = K(x*, Z) L^-T, tmp2^T = tmp1^T LB^-T."""
         x = x if x is not None else self.X
-        kern = self.kernel
         with torch.no_grad():
             st = self._state_for_predict(x)
-            f_uu, fB = st.f_uu, st.fB
-            ns, m, dy = x_new.shape[0], self.Z.shape[0], self.Y.shape[1]
-            T1 = _ops.padded_like_factor(f_uu, ns)
-            T1[:ns, :m] = kern.K(x_new, self.Z.detach())
-            f_uu.solve_right_lt(T1, ns)
-            T2 = T1.clone()
-            fB.solve_right_lt(T2, ns)
-            kp = _ops.round_up(m, 16)
-            mean = _ops.gemm_nt(T2, fB.A[m:], ns, dy, kp) + self.mean_function(x_new)
-            if diag:
-                v = kern.Kdiag(x_new).detach() - _ops.row_sumsq(T1, ns, m) + _ops.row_sumsq(T2, ns, m)
-                return mean, v[:, None].expand_as(mean)
-            cov = kern.K(x_new).clone()
-            _ops.gemm_nt(T2, T2, ns, ns, kp, alpha=1.0, beta=1.0, C=cov)
-            _ops.gemm_nt(T1, T1, ns, ns, kp, alpha=-1.0, beta=1.0, C=cov)
-        return mean, cov
+            T2c, cov = self._collapsed_predict(st.f_uu, st.fB, x_new, diag)
+            return T2c + self.mean_function(x_new), cov

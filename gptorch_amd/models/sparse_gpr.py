@@ -38,6 +38,7 @@ SVGP (sparse_gpr.py:198-381) follows VFE below: a minibatch bound over the same 
 (csrc/svgp.hip).  FITC (sparse_gpr.py:76-90, an empty class in the reference) lives in models/_fitc.py: the same streamed pipeline
 (_stream_gram) with its own row kernels (csrc/fitc.hip) between the right-solve and the accumulation.
 """
+import functools
 import math
 
 import numpy as np
@@ -109,6 +110,56 @@ class _InducingPointsGP(GPModel):
     def num_inducing(self) -> int:
         return self.Z.shape[0]
 
+    def _native_kernel(self):
+        """the kernel if it is one of the native stationary kinds (fused assembly + native sweeps),
+        else None (sums / products / Linear / static kernels: the kernel's own K and autograd)."""
+        from .. import kernels
+        k = self.kernel
+        return k if isinstance(k, kernels.Stationary) and k._kind is not None else None
+
+    def _kernel_adapter(self):
+        """-> (make_asm, tensors): the kernel tensors an autograd node differentiates, and what builds the adapter from them
+        inside the node (`make_asm(*tensors)`).  The ONE place the adapter is chosen: a native kind is differentiated w.r.t. its
+        constrained variance and length-scales, any other kernel object w.r.t. its raw parameters."""
+        k = self._native_kernel()
+        if k is not None:
+            return functools.partial(_NativeAsm, k._kind), [k.variance.transform(), k.length_scales.transform()]
+        return functools.partial(_GenericAsm, self.kernel), [p for p in self.kernel.parameters() if p.requires_grad]
+
+    def _data(self, x=None, y=None):
+        """(x, y) of an evaluation: the model's own data where none is given."""
+        x = x if x is not None else self.X
+        y = y if y is not None else self.Y
+        if not x.shape[0] == y.shape[0]:
+            raise ValueError("X and Y must have same # data.")
+        return x, y
+
+    def _collapsed_predict(self, f_uu, fB, x_new, diag):
+        """The predictive equations of a collapsed model (sparse_gpr.py:155-195) from its two factors, c^T in fB's extra rows:
+        -> (tmp2^T c, var [ns, dy] or cov [ns, ns]) with tmp1^T = K(x*, Z) L^-T, tmp2^T = tmp1^T LB^-T and
+        var = Kdiag(x*) - |tmp1|^2 + |tmp2|^2.  What turns tmp2^T c into the mean is the model's (VFE: / s2, FITC: + m(x*))."""
+        kern = self.kernel
+        ns, m, dy = x_new.shape[0], self.Z.shape[0], self.Y.shape[1]
+        T1 = _ops.padded_like_factor(f_uu, ns)                                    # tmp1^T = K(x*, Z) L^-T
+        T1[:ns, :m] = kern.K(x_new, self.Z.detach())
+        f_uu.solve_right_lt(T1, ns)
+        T2 = T1.clone()
+        fB.solve_right_lt(T2, ns)                                                 # tmp2^T = tmp1^T LB^-T
+        T2c = _ops.gemm_nt(T2, fB.A[m:], ns, dy, _ops.round_up(m, 16))            # tmp2^T c
+        if diag:
+            v = kern.Kdiag(x_new).detach() - _ops.row_sumsq(T1, ns, m) + _ops.row_sumsq(T2, ns, m)
+            return T2c, v[:, None].expand_as(T2c)
+        return T2c, _posterior_cov(kern.K(x_new), T2, T1, ns, m)
+
+
+def _posterior_cov(Kss, G, A, ns, m):
+    """K(x*) + G G^T - A A^T for [ns, m] factors G, A in zero-padded buffers (a fresh matrix: Kss is left as it is)."""
+    kp = _ops.round_up(m, 16)
+    cov = Kss.clone()
+    _ops.gemm_nt(G, G, ns, ns, kp, alpha=1.0, beta=1.0, C=cov)
+    _ops.gemm_nt(A, A, ns, ns, kp, alpha=-1.0, beta=1.0, C=cov)
+    return cov
+
 
 def _zeros(rows, cols, device):
     return torch.zeros(rows, cols, dtype=torch.float64, device=device)
@@ -148,11 +199,12 @@ class _State:
 
 
 class _NativeAsm:
-    """K(x_c, Z), K(Z) and their gradient sweeps for a kernel with a native kind: the fused assembly
-    kernel and the native sweeps (gpn_kernel_grad, gpn_kernel_grad_x2)."""
+    """K(x_c, Z), K(Z), Kdiag(x_c) and their gradient sweeps for a kernel with a native kind: the fused assembly
+    kernel and the native sweeps (gpn_kernel_grad, gpn_kernel_grad_x2).  Built from the constrained (variance, length_scales);
+    holds their detached values, and tensors() are the gradients w.r.t. these two, in this order and with their shapes."""
 
     def __init__(self, kind, var, ls):
-        self.kind, self.var, self.ls = kind, var, ls
+        self.kind, self.var, self.ls = kind, var.detach(), ls.detach()
 
     def factor_uu(self, Z):
         return _ops.kernel_factor(self.kind, Z, self.var, self.ls, None)          # L = chol(K(Z)) (+ladder)
@@ -163,7 +215,11 @@ class _NativeAsm:
     def trkff(self, x):
         return x.shape[0] * self.var[0]                                           # Kdiag = variance (kernels.py:174-179)
 
-    # -- backward: accumulators for (variance, length_scales, Z)
+    def kdiag(self, xc):
+        """-> (buffer, stride): Kdiag(x_c)[i] = buffer[i * stride]."""
+        return self.var, 0                                                        # Kdiag = variance for every row
+
+    # -- backward: accumulators for (variance, length_scales) and Z
     def begin(self, Z):
         self.g_var = torch.zeros(1, dtype=torch.float64, device=Z.device)
         self.g_ls = torch.zeros_like(self.ls)
@@ -181,21 +237,25 @@ class _NativeAsm:
         self.g_ls += gl
         _backward.kernel_backward_x2(self.kind, xc, Z, self.var, self.ls, G, out=self.g_Z)
 
-    def grad_trkff(self, coef, n_all):
+    def grad_kdiag(self, xc, gv):
+        self.g_var += gv.sum()
+
+    def grad_trkff(self, x, coef, n_all):
         self.g_var += coef * n_all                                                 # d tr Kff / d variance = N
 
     def tensors(self):
-        return [self.g_var, self.g_ls, self.g_Z]
+        return [self.g_var, self.g_ls]
 
 
 class _GenericAsm:
     """The same for ANY kernel object (sparse_gpr.py:126-129 takes whatever `self.kernel` is: sums,
     products, Linear, ...): K(x_c, Z) and K(Z) come from the kernel's own `K` (whose stationary
     leaves are the native assembly), and the gradient of sum(G * K) goes back through the kernel's own
-    autograd nodes, chunk by chunk -- to the RAW parameters directly, in `params` order."""
+    autograd nodes, chunk by chunk -- to the RAW parameters directly: built from those that require a gradient, and
+    tensors() are the gradients w.r.t. them, in their order."""
 
-    def __init__(self, kernel, params):
-        self.kernel, self.params = kernel, params
+    def __init__(self, kernel, *params):
+        self.kernel, self.params = kernel, list(params)
 
     def factor_uu(self, Z):
         with torch.no_grad():
@@ -208,6 +268,10 @@ class _GenericAsm:
     def trkff(self, x):
         with torch.no_grad():
             return self.kernel.Kdiag(x).sum()
+
+    def kdiag(self, xc):
+        with torch.no_grad():
+            return self.kernel.Kdiag(xc).contiguous(), 1
 
     def begin(self, Z):
         self.g_params = [torch.zeros_like(p) for p in self.params]
@@ -229,17 +293,25 @@ class _GenericAsm:
             Zg = Z.detach().requires_grad_(True)
             self._pull(self.kernel.K(xc, Zg), G, Zg)
 
-    def grad_trkff(self, coef, n_all):
+    def grad_kdiag(self, xc, gv):
+        with torch.enable_grad():
+            s = (self.kernel.Kdiag(xc) * gv).sum()
+            grads = torch.autograd.grad(s, self.params, allow_unused=True)
+        for acc, g in zip(self.g_params, grads):
+            if g is not None:
+                acc += g
+
+    def grad_trkff(self, x, coef, n_all):
         # row shards: every rank differentiates the diagonal of ITS rows; the all-reduce sums them
         with torch.enable_grad():
-            tr = self.kernel.Kdiag(self._x).sum()
+            tr = self.kernel.Kdiag(x).sum()
             grads = torch.autograd.grad(tr, self.params, allow_unused=True)
         for acc, g in zip(self.g_params, grads):
             if g is not None:
                 acc += coef * g
 
     def tensors(self):
-        return self.g_params + [self.g_Z]
+        return self.g_params
 
 
 def _stream_gram(asm, x, err, Z, f_uu, fB, scale, rows_hook=None):
@@ -388,19 +460,25 @@ def _sandwich(U, W, m):
     return R
 
 
+def _factor_inverses(f_uu, fB, m):
+    """what a collapsed backward starts from -> (U = L^-T, UB = LB^-T, B^-1 [m, m] symmetrised from its lower triangle)."""
+    U = _backward._upper_inverse(f_uu)                                     # L^-T
+    UB = _backward._upper_inverse(fB)                                      # LB^-T
+    Binv = _backward._kinv_lower(fB, UB)[:m, :m]
+    Binv = torch.tril(Binv) + torch.tril(Binv, -1).t()
+    return U, UB, Binv
+
+
 def _vfe_backward(asm, x, err, Z, st):
-    """-> dF/d noise [1] (constrained value); the kernel / inducing-point gradients are left in `asm`
-    (native kinds: w.r.t. the constrained variance / length-scales and Z; any other kernel: w.r.t. its
-    raw parameters and Z)."""
+    """-> (dF/d noise [1] (constrained value), None: err is the data, sparse_gpr.py:125); the kernel / inducing-point
+    gradients are left in `asm` (native kinds: w.r.t. the constrained variance / length-scales and Z; any other kernel:
+    w.r.t. its raw parameters and Z)."""
     dev = x.device
     n, p = err.shape
     m, s = Z.shape[0], st.s2
     f_uu, fB = st.f_uu, st.fB
     mp, pp = _ops.round_up(m, 16), _ops.round_up(p, 16)
-    U = _backward._upper_inverse(f_uu)                                     # L^-T
-    UB = _backward._upper_inverse(fB)                                      # LB^-T
-    Binv = _backward._kinv_lower(fB, UB)[:m, :m]
-    Binv = torch.tril(Binv) + torch.tril(Binv, -1).t()
+    U, UB, Binv = _factor_inverses(f_uu, fB, m)
     Bd = torch.tril(st.AAT[:m, :m]) + torch.tril(st.AAT[:m, :m], -1).t()
     Bd.diagonal().add_(1.0)
     eye = torch.eye(m, dtype=torch.float64, device=dev)
@@ -436,11 +514,10 @@ def _vfe_backward(asm, x, err, Z, st):
         Kx[:r, mp:mp + p] = err[c0:c0 + r]
         _ops.gemm_nt(Kx, Bq, r, m, ldk, alpha=1.0 / s, C=G)
         asm.grad_uf(xc, Z, G[:r, :m])
-    asm._x = x
-    asm.grad_trkff(-0.5 * p / s, n if SHARD_GROUP is not None else st.n_all)   # -p/(2s) d tr Kff (this rank's rows)
+    asm.grad_trkff(x, -0.5 * p / s, n if SHARD_GROUP is not None else st.n_all)   # -p/(2s) d tr Kff (this rank's rows)
 
     if SHARD_GROUP is not None:                                            # sum the row shards' contributions
-        for t in asm.tensors():
+        for t in asm.tensors() + [asm.g_Z]:
             _all_reduce(t)
     n_all = st.n_all
     c2 = st.terms[1] / (s * s)
@@ -448,7 +525,7 @@ def _vfe_backward(asm, x, err, Z, st):
     quad = _ops.dot2d(b, st.Aerr) / s - _ops.dot2d(b, b)                   # beta^T (B - I) beta
     g_noise = (0.5 * p / s) * (m - _ops.diag_sum(Binv, m)) - c2 / s + 0.5 * quad / s - 0.5 * p * st.tr / s \
         - 0.5 * p * n_all / s + 0.5 * (st.yy_all + p * st.trkff) / (s * s)
-    return g_noise.reshape(1)
+    return g_noise.reshape(1), None
 
 
 def _elbo(st, p, s2):
@@ -463,49 +540,35 @@ def _elbo(st, p, s2):
     return elbo
 
 
-class _VFEBound(torch.autograd.Function):
-    """The collapsed bound as one autograd node over (variance, length_scales, noise, Z)."""
+def _vfe_evaluate(asm, x, err, Z, noise):
+    """-> (the bound, its state, the (x, err) its backward streams over).  The noise is read on the host once per evaluation;
+    x and err are streamed as they come (row slices of either layout)."""
+    s2 = float(noise.item())
+    st = _vfe_forward(asm, x, err, Z, s2)
+    return _elbo(st, err.shape[1], s2), st, x, err
+
+
+class _CollapsedBound(torch.autograd.Function):
+    """A collapsed inducing-point likelihood (VFE's bound, FITC's marginal likelihood) as one autograd node over
+    (noise, Z, err, *kernel tensors of _InducingPointsGP._kernel_adapter).  The model brings
+    evaluate(asm, x, err, Z, noise) -> (value, state, x, err) and backward(asm, x, err, Z, state) -> (dF/d noise, dF/d err or
+    None) with the kernel / inducing-point gradients left in `asm`; the state is handed out through `holder`."""
 
     @staticmethod
-    def forward(ctx, variance, length_scales, noise, Z, kind, x, err, holder):
-        s2 = float(noise.item())
-        asm = _NativeAsm(kind, variance.detach(), length_scales.detach())
-        st = _vfe_forward(asm, x, err, Z.detach(), s2)
-        ctx.asm, ctx.x, ctx.err, ctx.st = asm, x, err, st
-        ctx.save_for_backward(length_scales, Z)
-        holder["state"] = st
-        return _elbo(st, err.shape[1], s2)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        length_scales, Z = ctx.saved_tensors
-        g_noise = _vfe_backward(ctx.asm, ctx.x, ctx.err, Z.detach(), ctx.st)
-        g_var, g_ls, g_Z = ctx.asm.tensors()
-        g = grad_out
-        return (g * g_var, g * g_ls.reshape(length_scales.shape), g * g_noise, g * g_Z,
-                None, None, None, None)
-
-
-class _VFEBoundGeneric(torch.autograd.Function):
-    """The same bound for any kernel object: node over (noise, Z, *raw kernel parameters)."""
-
-    @staticmethod
-    def forward(ctx, noise, Z, kernel, x, err, holder, *params):
-        s2 = float(noise.item())
-        asm = _GenericAsm(kernel, list(params))
-        st = _vfe_forward(asm, x, err, Z.detach(), s2)
-        ctx.asm, ctx.x, ctx.err, ctx.st = asm, x, err, st
+    def forward(ctx, evaluate, backward, make_asm, holder, x, noise, Z, err, *tensors):
+        ctx.asm, ctx.backward_fn = make_asm(*tensors), backward
+        value, ctx.st, ctx.x, ctx.err = evaluate(ctx.asm, x, err, Z.detach(), noise)
         ctx.save_for_backward(Z)
-        holder["state"] = st
-        return _elbo(st, err.shape[1], s2)
+        holder["state"] = ctx.st
+        return value
 
     @staticmethod
-    def backward(ctx, grad_out):
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
         Z, = ctx.saved_tensors
-        g_noise = _vfe_backward(ctx.asm, ctx.x, ctx.err, Z.detach(), ctx.st)
-        *g_params, g_Z = ctx.asm.tensors()
-        g = grad_out
-        return (g * g_noise, g * g_Z, None, None, None, None) + tuple(g * t for t in g_params)
+        g_noise, g_err = ctx.backward_fn(ctx.asm, ctx.x, ctx.err, Z.detach(), ctx.st)
+        return (None, None, None, None, None, g * g_noise, g * ctx.asm.g_Z, g * g_err if ctx.needs_input_grad[7] else None) \
+            + tuple(g * t for t in ctx.asm.tensors())
 
 
 class VFE(_InducingPointsGP):
@@ -513,32 +576,17 @@ class VFE(_InducingPointsGP):
         super().__init__(*args, **kwargs)
         assert isinstance(self.mean_function, Zero), "Mean functions not implemented for VFE yet."
 
-    def _native_kernel(self):
-        """the kernel if it is one of the native stationary kinds (fused assembly + native sweeps),
-        else None (sums / products / Linear / static kernels: the kernel's own K and autograd)."""
-        from .. import kernels
-        k = self.kernel
-        return k if isinstance(k, kernels.Stationary) and k._kind is not None else None
-
     def _bound(self, x):
-        k = self._native_kernel()
         holder = {}
         s2 = self.likelihood.variance.transform()
-        if k is not None:
-            elbo = _VFEBound.apply(k.variance.transform(), k.length_scales.transform(), s2, self.Z, k._kind, x,
-                                   self.Y, holder)                       # sparse_gpr.py:125 quirk: err = self.Y
-        else:
-            params = [p for p in self.kernel.parameters() if p.requires_grad]
-            elbo = _VFEBoundGeneric.apply(s2, self.Z, self.kernel, x, self.Y, holder, *params)
+        make_asm, tensors = self._kernel_adapter()
+        elbo = _CollapsedBound.apply(_vfe_evaluate, _vfe_backward, make_asm, holder, x, s2, self.Z,
+                                     self.Y, *tensors)                   # sparse_gpr.py:125 quirk: err = self.Y
         return elbo, holder["state"]
 
     def log_likelihood(self, x=None, y=None):
         """variational lower bound, sparse_gpr.py:108-153 (0-dim tensor)."""
-        x = x if x is not None else self.X
-        y = y if y is not None else self.Y
-        if not x.shape[0] == y.shape[0]:
-            raise ValueError("X and Y must have same # data.")
-        return self._bound(x)[0]
+        return self._bound(self._data(x, y)[0])[0]
 
     def _state_for_predict(self, x):
         """the M-sized state of the bound (chol K(Z), chol B, c) that a prediction starts from.  The reference re-evaluates the bound
@@ -550,25 +598,10 @@ class VFE(_InducingPointsGP):
     def _predict(self, x_new, diag=True, x=None):
         """sparse_gpr.py:155-195."""
         x = x if x is not None else self.X
-        kern = self.kernel
         with torch.no_grad():
             st = self._state_for_predict(x)
-            f_uu, fB, s2 = st.f_uu, st.fB, st.s2
-            ns, m, dy = x_new.shape[0], self.Z.shape[0], self.Y.shape[1]
-            T1 = _ops.padded_like_factor(f_uu, ns)                                    # tmp1^T = K(x*, Z) L^-T
-            T1[:ns, :m] = kern.K(x_new, self.Z.detach())
-            f_uu.solve_right_lt(T1, ns)
-            T2 = T1.clone()
-            fB.solve_right_lt(T2, ns)                                                 # tmp2^T = tmp1^T LB^-T
-            kp = _ops.round_up(m, 16)
-            mean = _ops.gemm_nt(T2, fB.A[m:], ns, dy, kp) / s2                        # tmp2^T c
-            if diag:
-                v = kern.Kdiag(x_new).detach() - _ops.row_sumsq(T1, ns, m) + _ops.row_sumsq(T2, ns, m)
-                return mean, v[:, None].expand_as(mean)
-            cov = kern.K(x_new).clone()
-            _ops.gemm_nt(T2, T2, ns, ns, kp, alpha=1.0, beta=1.0, C=cov)
-            _ops.gemm_nt(T1, T1, ns, ns, kp, alpha=-1.0, beta=1.0, C=cov)
-        return mean, cov
+            T2c, cov = self._collapsed_predict(st.f_uu, st.fB, x_new, diag)
+            return T2c / st.s2, cov                                                   # (the extra rows hold s2 c^T)
 
 
 # =====================================================================================================================
@@ -598,28 +631,6 @@ class VFE(_InducingPointsGP):
 GAUSSIAN_SHORTCUT = True   # likelihoods.Gaussian: the data term without the sqrt / square round trip of propagate_log's Normal
 
 
-class _SVGPNativeAsm(_NativeAsm):
-    def kdiag(self, xc):
-        return self.var, 0                                                 # Kdiag = variance for every row (kernels.py:174-179)
-
-    def grad_kdiag(self, xc, gv):
-        self.g_var += gv.sum()
-
-
-class _SVGPGenericAsm(_GenericAsm):
-    def kdiag(self, xc):
-        with torch.no_grad():
-            return self.kernel.Kdiag(xc).contiguous(), 1
-
-    def grad_kdiag(self, xc, gv):
-        with torch.enable_grad():
-            s = (self.kernel.Kdiag(xc) * gv).sum()
-            grads = torch.autograd.grad(s, self.params, allow_unused=True)
-        for acc, g in zip(self.g_params, grads):
-            if g is not None:
-                acc += g
-
-
 class _SVGPState:
     """the M-sized state of one evaluation (+ the single chunk's alpha and T, kept for the backward)."""
     __slots__ = ("f_uu", "betaT", "Q", "w", "kl", "saved", "nc")
@@ -630,10 +641,6 @@ def _sum_log_diag(A, m):
     _ops._native.check(_ops._native.lib().gpn_lml_reduce(_ops._stream(A.device), _ops._ptr(A), m, 0, A.stride(0), _ops._ptr(out)),
                        "gpn_lml_reduce")
     return out[0]
-
-
-def _svgp_chunk_rows(n):
-    return _chunk_rows(n)
 
 
 def _svgp_m_state(asm, Z, m_u, S_L):
@@ -680,7 +687,7 @@ def _svgp_forward(asm, x, Z, m_u, S_L):
     lib = _ops._native.lib()
     st = _svgp_m_state(asm, Z, m_u, S_L)
     ld = st.f_uu.ld
-    st.nc = nc = _svgp_chunk_rows(n)
+    st.nc = nc = _chunk_rows(n)
     f_mean = torch.empty(n, dy, dtype=torch.float64, device=dev)
     f_var = torch.empty(n, dtype=torch.float64, device=dev)
     At, T = _ops.zeros(nc + 16, ld, dev), _ops.zeros(nc, ld, dev)
@@ -768,33 +775,12 @@ def _grads_or_zero(g_mean, g_var, g_kl, f_mean, f_var):
 
 
 class _SVGPNode(torch.autograd.Function):
-    """q(f)'s marginals on a batch and KL(q(u) || p(u)) as one autograd node over (variance, length_scales, Z,
-    induced_output_mean, S_L): -> (f_mean0 [nb, dy], f_var [nb], KL)."""
+    """q(f)'s marginals on a batch and KL(q(u) || p(u)) as one autograd node over (Z, induced_output_mean, S_L, *kernel tensors
+    of _InducingPointsGP._kernel_adapter): -> (f_mean0 [nb, dy], f_var [nb], KL)."""
 
     @staticmethod
-    def forward(ctx, variance, length_scales, Z, m_u, S_L, kind, x):
-        asm = _SVGPNativeAsm(kind, variance.detach(), length_scales.detach())
-        f_mean, f_var, st = _svgp_forward(asm, x, Z.detach(), m_u.detach(), S_L.detach())
-        ctx.asm, ctx.x, ctx.st = asm, x, st
-        ctx.save_for_backward(length_scales, Z, S_L, f_mean, f_var)
-        return f_mean, f_var, st.kl
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g_mean, g_var, g_kl):
-        length_scales, Z, S_L, f_mean, f_var = ctx.saved_tensors
-        g_mean, g_var, g_kl = _grads_or_zero(g_mean, g_var, g_kl, f_mean, f_var)
-        g_m, g_S = _svgp_backward(ctx.asm, ctx.x, Z.detach(), S_L.detach(), ctx.st, g_mean, g_var, g_kl)
-        g_v, g_ls, g_Z = ctx.asm.tensors()
-        return g_v, g_ls.reshape(length_scales.shape), g_Z, g_m, g_S, None, None
-
-
-class _SVGPNodeGeneric(torch.autograd.Function):
-    """The same node for any kernel object: over (Z, induced_output_mean, S_L, *raw kernel parameters)."""
-
-    @staticmethod
-    def forward(ctx, Z, m_u, S_L, kernel, x, *params):
-        asm = _SVGPGenericAsm(kernel, list(params))
+    def forward(ctx, make_asm, x, Z, m_u, S_L, *tensors):
+        asm = make_asm(*tensors)
         f_mean, f_var, st = _svgp_forward(asm, x, Z.detach(), m_u.detach(), S_L.detach())
         ctx.asm, ctx.x, ctx.st = asm, x, st
         ctx.save_for_backward(Z, S_L, f_mean, f_var)
@@ -806,8 +792,7 @@ class _SVGPNodeGeneric(torch.autograd.Function):
         Z, S_L, f_mean, f_var = ctx.saved_tensors
         g_mean, g_var, g_kl = _grads_or_zero(g_mean, g_var, g_kl, f_mean, f_var)
         g_m, g_S = _svgp_backward(ctx.asm, ctx.x, Z.detach(), S_L.detach(), ctx.st, g_mean, g_var, g_kl)
-        *g_params, g_Z = ctx.asm.tensors()
-        return (g_Z, g_m, g_S, None, None) + tuple(g_params)
+        return (None, None, ctx.asm.g_Z, g_m, g_S) + tuple(ctx.asm.tensors())
 
 
 # ---- host-side initialisation (sparse_gpr.py:310-335): runs once on <= 100 points, before the model moves to the GPU ------
@@ -894,20 +879,11 @@ class SVGP(_InducingPointsGP):
         dev = self.Z.device
         return Param(m_u.to(dev)), Param(chol_cov.to(dev), transform=LowerCholeskyTransform())
 
-    def _native_kernel(self):
-        from .. import kernels
-        k = self.kernel
-        return k if isinstance(k, kernels.Stationary) and k._kind is not None else None
-
     def _marginals(self, x):
         """-> (f_mean0 [n, dy] without the mean function, f_var [n], KL) through the native node."""
-        k = self._native_kernel()
         S_L = self.induced_output_chol_cov.transform()
-        if k is not None:
-            return _SVGPNode.apply(k.variance.transform(), k.length_scales.transform(), self.Z, self.induced_output_mean, S_L,
-                                   k._kind, x)
-        params = [p for p in self.kernel.parameters() if p.requires_grad]
-        return _SVGPNodeGeneric.apply(self.Z, self.induced_output_mean, S_L, self.kernel, x, *params)
+        make_asm, tensors = self._kernel_adapter()
+        return _SVGPNode.apply(make_asm, x, self.Z, self.induced_output_mean, S_L, *tensors)
 
     def _data_term(self, f_mean, f_var, y):
         """sum over output columns of likelihood.propagate_log(N(f_mean_j, f_var), y_j), sparse_gpr.py:276-283."""
@@ -933,8 +909,7 @@ class SVGP(_InducingPointsGP):
             x, y = self.X[i, :], self.Y[i, :]
         else:
             x, y = self.X, self.Y
-        if not x.shape[0] == y.shape[0]:
-            raise ValueError("X and Y must have same # data.")
+        x, y = self._data(x, y)
         f_mean0, f_var, kl = self._marginals(x)
         f_mean = f_mean0 + self.mean_function(x)
         return self._data_term(f_mean, f_var, y) * (self.num_data / x.shape[0]) - kl
@@ -944,9 +919,8 @@ class SVGP(_InducingPointsGP):
         with torch.no_grad():
             Z, m_u = self.Z.detach(), self.induced_output_mean.detach()
             S_L = self.induced_output_chol_cov.transform().detach()
-            k = self._native_kernel()
-            asm = _SVGPNativeAsm(k._kind, k.variance.transform().detach(), k.length_scales.transform().detach()) \
-                if k is not None else _SVGPGenericAsm(self.kernel, [])
+            make_asm, tensors = self._kernel_adapter()
+            asm = make_asm(*tensors)
             mu_x = self.mean_function(x_new)
             if diag:
                 f_mean0, f_var, _ = _svgp_forward(asm, x_new, Z, m_u, S_L)
@@ -964,7 +938,4 @@ class SVGP(_InducingPointsGP):
             wT = _zeros(_ops.round_up(dy, 16), f_uu.ld, x_new.device)
             wT[:dy, :m] = st.w.t()
             f_mean = _ops.gemm_nt(At, wT, ns, dy, kp) + mu_x
-            cov = self.kernel.K(x_new).clone()
-            _ops.gemm_nt(Gm, Gm, ns, ns, kp, alpha=1.0, beta=1.0, C=cov)
-            _ops.gemm_nt(At, At, ns, ns, kp, alpha=-1.0, beta=1.0, C=cov)
-        return f_mean, cov
+            return f_mean, _posterior_cov(self.kernel.K(x_new), Gm, At, ns, m)
