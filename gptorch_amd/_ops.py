@@ -602,6 +602,32 @@ def diag_sum(A, m):
     return dot2d_raw(_ptr(A), A.stride(0) + 1, 0, None, 0, 0, m, 1, 1, A.device)[0]
 
 
+def lik_expect(kind, params, f_mean, f_var, y, nodes, weights, want_value=True, want_mean=True, want_var=True, want_params=True):
+    """gpn_lik_expect: the Gauss-Hermite expectation of a non-Gaussian log-likelihood under N(f_mean[:, k], f_var) summed over
+    the entries, with its gradients -> (value 0-dim, g_mean [rows, dy], g_var [rows], g_params [2]); an output that is not
+    wanted is None.  params: a [2] device tensor (Student-t: df, scale^2) or None; nodes / weights: [H] device tensors of
+    the rule (None for the Poisson closed form).  ONE call, no host synchronisation."""
+    _req(params, f_mean, f_var, y, nodes, weights)
+    if f_mean.dim() != 2 or tuple(y.shape) != tuple(f_mean.shape) or f_var.shape != (f_mean.shape[0],):
+        raise ValueError("expect f_mean [rows, dy], y [rows, dy] and f_var [rows]; got %s, %s, %s"
+                         % (tuple(f_mean.shape), tuple(y.shape), tuple(f_var.shape)))
+    f_mean = f_mean if f_mean.stride(1) == 1 else f_mean.contiguous()
+    y = y if y.stride(1) == 1 else y.contiguous()
+    f_var = _c(f_var)
+    rows, dy = f_mean.shape
+    dev = f_mean.device
+    work = torch.empty(2 * ((rows + _native.LIK_ROWS_PER_GROUP - 1) // _native.LIK_ROWS_PER_GROUP), dtype=torch.float64, device=dev)
+    value = torch.empty((), dtype=torch.float64, device=dev) if want_value else None
+    g_mean = torch.empty(rows, dy, dtype=torch.float64, device=dev) if want_mean else None
+    g_var = torch.empty(rows, dtype=torch.float64, device=dev) if want_var else None
+    g_params = torch.empty(2, dtype=torch.float64, device=dev) if want_params else None
+    st = _native.lib().gpn_lik_expect(_stream(dev), kind, _ptr(params), _ptr(f_mean), f_mean.stride(0), _ptr(f_var), _ptr(y), y.stride(0),
+                                      rows, dy, _ptr(nodes), _ptr(weights), 0 if nodes is None else nodes.numel(), _ptr(work),
+                                      work.numel() * 8, _ptr(value), _ptr(g_mean), dy, _ptr(g_var), _ptr(g_params))
+    _native.check(st, "gpn_lik_expect")
+    return value, g_mean, g_var, g_params
+
+
 def padded_like_factor(f, m):
     """zeroed [round_up(m,128), f.ld] buffer for right-hand sides of solve_right_lt."""
     return zeros(round_up(max(m, 1), LEAF), f.ld, f.device)

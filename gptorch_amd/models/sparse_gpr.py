@@ -629,6 +629,52 @@ class VFE(_InducingPointsGP):
 # log-determinant's share Phi(L^T diag(1 / L_ii)) = I / 2 turns the "+ g_kl dy (Q + I)" of G_beta beta^T into "+ g_kl dy Q".
 # Checked against autograd through the reference's op chain by tests/golden/make_svgp_golden.py.
 GAUSSIAN_SHORTCUT = True   # likelihoods.Gaussian: the data term without the sqrt / square round trip of propagate_log's Normal
+# likelihoods.Bernoulli / Poisson / StudentT on the GPU: the data term and its gradients from ONE fused launch (csrc/lik.hip,
+# gpn_lik_expect) instead of the torch ops of Likelihood.propagate_log on an [nb, H] tensor per column and their autograd twins
+NATIVE_EXPECTATION = True
+
+
+class _LikExpectNode(torch.autograd.Function):
+    """The Gauss-Hermite expectation of a non-Gaussian log-likelihood as one autograd node over (f_mean [nb, dy], f_var [nb],
+    y, *likelihood tensors): gpn_lik_expect once in the forward, which also leaves the gradients; the backward hands them back.
+    `tensors`: () or, for Student-t, (scale^2 [1],) -- the constrained value, so the Param's transform is autograd's."""
+
+    @staticmethod
+    def forward(ctx, kind, df, H, f_mean, f_var, y, *tensors):
+        dev = f_mean.device
+        params = torch.cat([torch.full((1,), float(df), dtype=torch.float64, device=dev), tensors[0].detach().reshape(1)]) if tensors else None
+        nodes, weights = (None, None) if kind == _ops._native.LIK_POISSON else _likelihood_rule(H, dev)
+        value, g_mean, g_var, g_params = _ops.lik_expect(kind, params, f_mean.detach(), f_var.detach(), y.detach(), nodes, weights,
+                                                         want_params=bool(tensors))
+        ctx.save_for_backward(g_mean, g_var, g_params)
+        ctx.shapes = [t.shape for t in tensors]
+        return value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        g_mean, g_var, g_params = ctx.saved_tensors
+        return (None, None, None, g * g_mean, g * g_var, None) + tuple((g * g_params[1]).reshape(s) for s in ctx.shapes)
+
+
+def _likelihood_rule(H, device):
+    from .. import likelihoods
+    return likelihoods.gauss_hermite(H, device)
+
+
+def _native_likelihood(lik):
+    """-> (kind, df, tensors) of gpn_lik_expect for a likelihood whose type is EXACTLY one of the four native ones, else None
+    (Gaussian, user likelihoods and subclasses -- which may override logp -- keep their propagate_log)."""
+    from .. import likelihoods
+    nat = _ops._native
+    if type(lik) is likelihoods.Bernoulli:
+        return (nat.LIK_PROBIT if lik.link == "probit" else nat.LIK_LOGIT), 0.0, ()
+    if type(lik) is likelihoods.Poisson:
+        return nat.LIK_POISSON, 0.0, ()
+    if type(lik) is likelihoods.StudentT:
+        s = lik.scale.transform()
+        return nat.LIK_STUDENT_T, lik.df, (s * s,)
+    return None
 
 
 class _SVGPState:
@@ -895,6 +941,10 @@ class SVGP(_InducingPointsGP):
             n = y.nelement()
             return (-0.5 * (n * (math.log(2.0 * math.pi) + torch.log(s2))
                             + (torch.sum((y - f_mean) ** 2) + y.shape[1] * f_var.sum()) / s2)).reshape(())
+        native = _native_likelihood(lik) if NATIVE_EXPECTATION and f_mean.is_cuda else None
+        if native is not None:
+            kind, df, tensors = native
+            return _LikExpectNode.apply(kind, df, lik.num_gauss_hermite_points, f_mean, f_var, y, *tensors)
         sd = torch.sqrt(f_var)
         return torch.stack([lik.propagate_log(torch.distributions.Normal(f_mean[:, j], sd), y[:, j]).reshape(())
                             for j in range(y.shape[1])]).sum()

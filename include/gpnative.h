@@ -694,6 +694,33 @@ int gpn_fitc_backward_rows(void* stream, const double* alpha, int64_t lda, doubl
                            const double* beta, int64_t ldb, int dy, const double* err, const double* lambda, double* r_out,
                            double* g_out, double* alphaT, double* galphaT, int64_t ldo);
 
+/* ---- non-Gaussian likelihoods (gptorch_amd/likelihoods.py): the expected log-likelihood by Gauss-Hermite quadrature -------
+ * The data term of SVGP (sparse_gpr.py:276-283) for a likelihood whose expectation has no closed form -- the quadrature
+ * the reference's likelihoods.py names and leaves as a TODO.  With f_mean [rows, dy] (ldf), f_var [rows] (one variance per
+ * row, shared by its dy columns), y [rows, dy] (ldy) and the H <= 64 nodes x_h and weights w_h of the physicists' rule
+ * (numpy.polynomial.hermite.hermgauss(H)), all device pointers:
+ *   value[0]       = sum_{i,k} pi^-1/2 sum_h w_h logp(f_ikh, y_ik),   f_ikh = f_mean_ik + sqrt(2 f_var_i) x_h
+ *   g_mean[i, k]   = pi^-1/2 sum_h w_h logp'(f_ikh)                                  (ldg)
+ *   g_var[i]       = sum_k pi^-1/2 sum_h w_h logp'(f_ikh) x_h / sqrt(2 f_var_i)
+ *   g_params[0..1] = (0, d value / d params[1])
+ * -- the gradients are the exact derivatives of the discrete rule, so value and gradients are consistent to rounding.
+ * kind: GPN_LIK_PROBIT   y in {0, 1}, logp = log Phi((2y - 1) f)          (stable in both tails)
+ *       GPN_LIK_LOGIT    y in {0, 1}, logp = log sigma((2y - 1) f)        (no overflow at any |f|)
+ *       GPN_LIK_POISSON  log link; the CLOSED form y mu - exp(mu + v/2) - lgamma(y + 1) for value and gradients: nodes,
+ *                        weights and H are not read
+ *       GPN_LIK_STUDENT_T  params = (df, scale^2) on the device (NULL for the other kinds); df is a fixed shape parameter,
+ *                        g_params[0] is written as 0
+ * Each of value, g_mean, g_var, g_params may be NULL.  f_var < 0 gives NaN.  ONE pass over the entries; sums in a fixed order
+ * (per-lane sums, a shuffle tree, per-workgroup partials in `work`, a second single-workgroup launch), no atomics: the same
+ * call twice gives the same bits.  work: work_bytes >= 16 * ceil(rows / GPN_LIK_ROWS_PER_GROUP) bytes.  Nothing is
+ * synchronised or read back: the call may be captured. */
+enum { GPN_LIK_PROBIT = 0, GPN_LIK_LOGIT = 1, GPN_LIK_POISSON = 2, GPN_LIK_STUDENT_T = 3 };
+#define GPN_LIK_ROWS_PER_GROUP 256
+int gpn_lik_expect(void* stream, int kind, const double* params, const double* f_mean, int64_t ldf, const double* f_var,
+                   const double* y, int64_t ldy, int64_t rows, int dy, const double* nodes, const double* weights, int H,
+                   double* work, int64_t work_bytes, double* value, double* g_mean, int64_t ldg, double* g_var,
+                   double* g_params);
+
 
 /* ---- optional launch profiler (bench.py's roofline legs) ---------------------- */
 /* While enabled, every contraction / assembly / gradient-sweep / leaf launch of this library is bracketed by two HIP events
