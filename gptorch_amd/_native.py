@@ -120,6 +120,19 @@ SIGNATURES = {
     "gpn_refine_finish": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "gpn_lik_expect": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    # LaplaceGP (csrc/laplace.hip; the back-substitution: csrc/refine.hip)
+    "gpn_lik_derivs_work_bytes": (c_int64, [c_int64]),
+    "gpn_lik_derivs": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gpn_laplace_system": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64]),
+    "gpn_laplace_rows_work_bytes": (c_int64, [c_int64]),
+    "gpn_laplace_matvec": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "gpn_laplace_diag": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                 c_void_p, c_void_p]),
+    "gpn_laplace_grad_work_bytes": (c_int64, [c_int64, c_int]),
+    "gpn_laplace_grad": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
+                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gpn_backsub_work_bytes": (c_int64, [c_int64, c_int]),
+    "gpn_backsub": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64]),
 }
 LIK_PROBIT, LIK_LOGIT, LIK_POISSON, LIK_STUDENT_T = 0, 1, 2, 3   # include/gpnative.h GPN_LIK_*
 LIK_ROWS_PER_GROUP = 256                                        # GPN_LIK_ROWS_PER_GROUP

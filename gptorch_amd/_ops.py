@@ -628,6 +628,104 @@ def lik_expect(kind, params, f_mean, f_var, y, nodes, weights, want_value=True, 
     return value, g_mean, g_var, g_params
 
 
+# ----------------------------------------------------------------------------
+# LaplaceGP (models/laplace.py): csrc/laplace.hip + the back-substitution of csrc/refine.hip
+# ----------------------------------------------------------------------------
+def _vec(t, n, what):
+    _req(t)
+    if t.numel() != n:
+        raise ValueError("%s must have %d entries; got %s" % (what, n, tuple(t.shape)))
+    return _c(t.detach().reshape(-1))
+
+
+def _kargs(X, variance, length_scales):
+    _req(X, variance, length_scales)
+    Xc, var, ls = _c(X.detach()), _c(variance.detach()), _c(length_scales.detach())
+    return Xc, var, ls, (_ptr(Xc), Xc.shape[0], Xc.shape[1], _ptr(var), _ptr(ls), ls.numel())
+
+
+def lik_derivs(kind, f, y, want_value=True, want_d1=True, want_w=True, want_d3=True):
+    """gpn_lik_derivs: sum log p(y_i | f_i) and, per point, d1 = dlp/df, W = -d2lp/df2, d3 = d3lp/df3 ->
+    (value 0-dim, d1 [n], W [n], d3 [n]); an output that is not wanted is None.  No host synchronisation."""
+    n = f.numel()
+    f, y = _vec(f, n, "f"), _vec(y, n, "y")
+    dev = f.device
+    lib = _native.lib()
+    work = torch.empty(max(1, int(lib.gpn_lik_derivs_work_bytes(n)) // 8), dtype=torch.float64, device=dev)
+    outs = [torch.empty((), dtype=torch.float64, device=dev) if want_value else None]
+    outs += [torch.empty(n, dtype=torch.float64, device=dev) if want else None for want in (want_d1, want_w, want_d3)]
+    st = lib.gpn_lik_derivs(_stream(dev), kind, _ptr(f), _ptr(y), n, _ptr(work), work.numel() * 8, *[_ptr(o) for o in outs])
+    _native.check(st, "gpn_lik_derivs")
+    return tuple(outs)
+
+
+def laplace_system(kind, X, variance, length_scales, s, out, ldo):
+    """gpn_laplace_system: B = I + diag(s) K(X) diag(s), the entries on and below the diagonal, into `out` (leading dimension
+    ldo; a factor buffer)."""
+    Xc, var, ls, args = _kargs(X, variance, length_scales)
+    s = _vec(s, Xc.shape[0], "s")
+    _req(out)
+    st = _native.lib().gpn_laplace_system(_stream(Xc.device), KINDS[kind], *args, _ptr(s), _ptr(out), ldo)
+    _native.check(st, "gpn_laplace_system")
+    return out
+
+
+def _rows_work(n, device, work):
+    need = max(1, int(_native.lib().gpn_laplace_rows_work_bytes(n)) // 8)
+    return work if (work is not None and work.numel() >= need and work.device == device) else torch.empty(need, dtype=torch.float64, device=device)
+
+
+def laplace_matvec(kind, X, variance, length_scales, v, work=None):
+    """gpn_laplace_matvec: K(X) v [n], matrix-free (work: a buffer of an earlier call to reuse)."""
+    Xc, var, ls, args = _kargs(X, variance, length_scales)
+    n = Xc.shape[0]
+    v = _vec(v, n, "v")
+    work = _rows_work(n, Xc.device, work)
+    out = torch.empty(n, dtype=torch.float64, device=Xc.device)
+    st = _native.lib().gpn_laplace_matvec(_stream(Xc.device), KINDS[kind], *args, _ptr(v), _ptr(work), _ptr(out))
+    _native.check(st, "gpn_laplace_matvec")
+    return out
+
+
+def laplace_diag(kind, X, variance, length_scales, s, Binv, work=None):
+    """gpn_laplace_diag: diag((K^-1 + W)^-1) [n] = (1 / s_i) sum_j K_ij s_j Binv_ji, Binv (row-major, lower triangle read)."""
+    Xc, var, ls, args = _kargs(X, variance, length_scales)
+    n = Xc.shape[0]
+    s = _vec(s, n, "s")
+    _req(Binv)
+    work = _rows_work(n, Xc.device, work)
+    out = torch.empty(n, dtype=torch.float64, device=Xc.device)
+    st = _native.lib().gpn_laplace_diag(_stream(Xc.device), KINDS[kind], *args, _ptr(s), _ptr(Binv), Binv.stride(0), _ptr(work), _ptr(out))
+    _native.check(st, "gpn_laplace_diag")
+    return out
+
+
+def laplace_grad(kind, X, variance, length_scales, s, Binv, a, u, d1):
+    """gpn_laplace_grad: sum_ij G_ij dK_ij/d(variance, length_scales) [1 + nls] (CONSTRAINED values) with
+    G = 1/2 a a^T - 1/2 diag(s) Binv diag(s) + 1/2 (u d1^T + d1 u^T)."""
+    Xc, var, ls, args = _kargs(X, variance, length_scales)
+    n = Xc.shape[0]
+    s, a, u, d1 = _vec(s, n, "s"), _vec(a, n, "a"), _vec(u, n, "u"), _vec(d1, n, "d1")
+    _req(Binv)
+    lib = _native.lib()
+    work = torch.empty(max(1, int(lib.gpn_laplace_grad_work_bytes(n, ls.numel())) // 8), dtype=torch.float64, device=Xc.device)
+    out = torch.empty(1 + ls.numel(), dtype=torch.float64, device=Xc.device)
+    st = lib.gpn_laplace_grad(_stream(Xc.device), KINDS[kind], *args, _ptr(s), _ptr(Binv), Binv.stride(0), _ptr(a), _ptr(u), _ptr(d1),
+                              _ptr(work), _ptr(out))
+    _native.check(st, "gpn_laplace_grad")
+    return out
+
+
+def backsub(f):
+    """gpn_backsub: (L^-T alpha)^T [e, n] for the alpha^T in the extra rows of a factorised buffer."""
+    lib = _native.lib()
+    work = torch.empty(max(1, int(lib.gpn_backsub_work_bytes(f.n, f.e)) // 8), dtype=torch.float64, device=f.device)
+    out = torch.empty(f.e, f.n, dtype=torch.float64, device=f.device)
+    st = lib.gpn_backsub(_stream(f.device), _ptr(f.A), f.ld, _ptr(f.winv), f.n, f.e, _ptr(work), _ptr(out), f.n)
+    _native.check(st, "gpn_backsub")
+    return out
+
+
 def padded_like_factor(f, m):
     """zeroed [round_up(m,128), f.ld] buffer for right-hand sides of solve_right_lt."""
     return zeros(round_up(max(m, 1), LEAF), f.ld, f.device)

@@ -97,6 +97,9 @@ int pack_rhs_full(hipStream_t s, const double* Y, const double* M, int64_t n, in
 // K(X) + noise I (lower tiles) into A and into Ksave (kmat.hip; gpn_lml_forward_saving)
 int assemble_lower_saving(hipStream_t s, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
                           int nls, const double* noise, double* A, double* Ksave, int64_t lda);
+// I + diag(sc) K(X) diag(sc), the entries on and below the diagonal only (kmat.hip; gpn_laplace_system)
+int assemble_laplace_system(hipStream_t s, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
+                            int nls, const double* sc, double* A, int64_t lda);
 // K(X_b) + noise_b I (lower tiles) + right-hand sides + info words of `batch` models (kmat.hip; gpn_lml_forward_batched)
 int assemble_batched(hipStream_t s, int kind, int batch, const double* X, int64_t sX, int64_t n, int d, const double* Y, int64_t sY,
                      const double* M, int64_t sM, int dy, const double* variance, const double* length_scales, int nls,

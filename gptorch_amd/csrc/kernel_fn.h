@@ -27,4 +27,41 @@ __device__ __forceinline__ double kernel_of_r2(double r2, double var) {
   }
 }
 
+// K and the base B of its length-scale derivative, dK/d(ell_d) = B(r) s_d / ell_d with s_d = ((x_id - x_jd) / ell_d)^2 -- the
+// gradient sweeps (grad.hip, laplace.hip)
+template <int KIND>
+__device__ __forceinline__ void k_and_base(double r2, double var, double& K, double& B) {
+  if constexpr (KIND == GPN_RBF) {
+    K = var * exp(-0.5 * r2);
+    B = K;
+  } else if constexpr (KIND == GPN_SQDIST) {
+    // util.squared_distance itself (util.py:73-88): K = r^2, no variance.  B = -2 dK/d(r^2) = -2
+    // everywhere, also at r = 0 (direct differences: nothing is clamped, so the second derivative
+    // the reference guards with its detach() trick, test_util.py:78-106, is the plain 2)
+    K = 0.0;
+    B = -2.0;
+  } else {
+    const bool dead = r2 < 1e-40;                 // kernels.py:172 clamp: no gradient below it
+    const double r = sqrt(fmax(r2, 1e-40));
+    if constexpr (KIND == GPN_MATERN52) {
+      const double s5 = 2.23606797749978969641;
+      const double e = exp(-s5 * r);
+      K = var * (1.0 + s5 * r + 5.0 / 3.0 * r * r) * e;
+      B = dead ? 0.0 : var * (5.0 / 3.0) * (1.0 + s5 * r) * e;
+    } else if constexpr (KIND == GPN_MATERN32) {
+      const double s3 = 1.73205080756887729353;
+      const double e = exp(-s3 * r);
+      K = var * (1.0 + s3 * r) * e;
+      B = dead ? 0.0 : 3.0 * var * e;
+    } else if constexpr (KIND == GPN_PERIODIC) {
+      K = var * cos(r);
+      B = dead ? 0.0 : var * sin(r) / r;
+    } else {
+      const double e = exp(-r);
+      K = var * e;
+      B = dead ? 0.0 : var * e / r;
+    }
+  }
+}
+
 }  // namespace gpn

@@ -39,9 +39,13 @@ struct KmatArgs {
   // gpn_lml_forward_saving: every entry is also stored here (same leading dimension) -- a pristine copy of Kyy for the refinement
   // step's residual pass, which otherwise re-computes every entry (the factorisation overwrites K in place)
   double* K2 = nullptr;
+  // gpn_laplace_system (LAPLACE instantiations only; symmetric lower): sqrt(W) of LaplaceGP's Newton step, n entries
+  const double* sc = nullptr;
 };
 
-template <int KIND>
+// LAPLACE (compile-time: the other instantiations are untouched): the entry becomes B_ij = delta_ij + s_i s_j k_ij, and only
+// the entries on and below the diagonal are written (a factor buffer whose strict upper triangle stays as it was)
+template <int KIND, bool LAPLACE = false>
 __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs p) {
   __shared__ __attribute__((aligned(16))) double xs[DC][KT];   // row points
   __shared__ __attribute__((aligned(16))) double ys[DC][KT];   // column points
@@ -149,6 +153,21 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs p) {
           if (col + 1 >= nreal) v1 = 0.0;
         }
       }
+      if constexpr (LAPLACE) {
+        if (col > row) continue;                 // (row < n = m: col and, where it is written, col + 1 lie inside the matrix)
+        const double si = p.sc[row];
+        v0 = (si * p.sc[col]) * v0;
+        if (row == col) v0 += 1.0;
+        if (col + 1 <= row) {
+          v1 = (si * p.sc[col + 1]) * v1;
+          if (row == col + 1) v1 += 1.0;
+          if (p.vec_ok) *reinterpret_cast<d2*>(krow + col) = d2{v0, v1};
+          else { krow[col] = v0; krow[col + 1] = v1; }
+        } else {
+          krow[col] = v0;
+        }
+        continue;
+      }
       if (p.vec_ok && col + 1 < p.m) {
         *reinterpret_cast<d2*>(krow + col) = d2{v0, v1};
         if (p.K2) *reinterpret_cast<d2*>(p.K2 + (int64_t)row * p.ldk + col) = d2{v0, v1};
@@ -219,6 +238,34 @@ int assemble_lower_saving(hipStream_t s, int kind, const double* X, int64_t n, i
     case GPN_MATERN32: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, a); break;
     case GPN_EXP: hipLaunchKernelGGL(kmat_kernel<GPN_EXP>, grid, dim3(256), 0, s, a); break;
     default: hipLaunchKernelGGL(kmat_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, a); break;
+  }
+  if (rec >= 0) profile_end(s, rec);
+  GPN_LAUNCH_CHECK();
+  return GPN_OK;
+}
+
+// B = I + diag(sc) K(X) diag(sc), entries on and below the diagonal, into A (laplace.hip; gpn_laplace_system)
+int assemble_laplace_system(hipStream_t s, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
+                            int nls, const double* sc, double* A, int64_t lda) {
+  KmatArgs a;
+  a.X = X; a.X2 = X;
+  a.variance = variance; a.ls = length_scales; a.noise = nullptr; a.sc = sc;
+  a.K = A; a.ldk = lda;
+  a.n = (int)n; a.m = (int)n; a.d = d; a.nls = nls;
+  a.symmetric = 1; a.lower = 1;
+  a.vec_ok = ((lda & 1) == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);
+  a.sX = 0; a.sK = 0;
+  const unsigned tm = (unsigned)((n + KT - 1) / KT);
+  const dim3 grid(tm * (tm + 1) / 2);
+  int rec = -1;
+  if (profile_on()) rec = profile_begin(s, 8.0 * (0.5 * n * (n + 1.0) + (double)n * d), PROF_KMAT);
+  switch (kind) {
+    case GPN_RBF: hipLaunchKernelGGL((kmat_kernel<GPN_RBF, true>), grid, dim3(256), 0, s, a); break;
+    case GPN_MATERN52: hipLaunchKernelGGL((kmat_kernel<GPN_MATERN52, true>), grid, dim3(256), 0, s, a); break;
+    case GPN_MATERN32: hipLaunchKernelGGL((kmat_kernel<GPN_MATERN32, true>), grid, dim3(256), 0, s, a); break;
+    case GPN_EXP: hipLaunchKernelGGL((kmat_kernel<GPN_EXP, true>), grid, dim3(256), 0, s, a); break;
+    case GPN_PERIODIC: hipLaunchKernelGGL((kmat_kernel<GPN_PERIODIC, true>), grid, dim3(256), 0, s, a); break;
+    default: return -2;
   }
   if (rec >= 0) profile_end(s, rec);
   GPN_LAUNCH_CHECK();

@@ -853,3 +853,30 @@ extern "C" int gpn_refine_finish(void* stream, const double* Y, const double* M,
   GPN_LAUNCH_CHECK();
   return GPN_OK;
 }
+
+// the back-substitution on its own (LaplaceGP's Newton step: B^-1 r = L^-T (L^-1 r), the forward half riding along the
+// factorisation as an extra row): work holds the s and a regions of the refinement's layout, out [dy, ldo] <- a_hat^T
+extern "C" int64_t gpn_backsub_work_bytes(int64_t n, int dy) {
+  if (n < 0 || dy <= 0) return 0;
+  return 2 * (int64_t)dy * round_up(n, LEAF) * (int64_t)sizeof(double);
+}
+
+extern "C" int gpn_backsub(void* stream, const double* A, int64_t lda, const double* winv, int64_t n, int dy, double* work,
+                           double* out, int64_t ldo) {
+  if (!A) return -2;
+  if (n < 0) return -5;
+  if (dy <= 0) return -6;
+  if (lda != gpn_factor_ld(n, dy)) return -3;
+  if (!winv) return -4;
+  if (!work) return -7;
+  if (!out) return -8;
+  if (ldo < n) return -9;
+  if (n == 0) return GPN_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const RefineLayout L = refine_layout(n, dy);
+  const int rc = refine_backsub(s, A, lda, winv, n, dy, work, L);
+  if (rc != GPN_OK) return rc;
+  GPN_HIP_CHECK(hipMemcpy2DAsync(out, ldo * sizeof(double), work + L.a, L.lds * sizeof(double), n * sizeof(double), dy,
+                                 hipMemcpyDeviceToDevice, s));
+  return GPN_OK;
+}

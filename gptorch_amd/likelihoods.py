@@ -8,7 +8,8 @@ The quadrature rule, for q(f) = N(mu, v) and the physicists' nodes x_h and weigh
 
 Everything in this file is plain torch (CPU or GPU, differentiable by autograd).  On the GPU, SVGP evaluates the data term of
 the four new classes with ONE fused kernel instead (csrc/lik.hip through models/sparse_gpr.py, NATIVE_EXPECTATION): the same
-rule and its exact derivatives.
+rule and its exact derivatives.  Bernoulli and Poisson also state logp_derivatives (logp and its first three derivatives in f):
+what models.LaplaceGP's Newton search needs, evaluated on the GPU by csrc/laplace.hip with the same closed forms.
 """
 import math
 
@@ -88,6 +89,11 @@ class Likelihood(Model):
 
     def logp(self, F, Y):
         raise NotImplementedError("%s defines no logp(F, Y)" % type(self).__name__)
+
+    def logp_derivatives(self, F, Y):
+        """-> (logp, d1 = dlogp/dF, W = -d2logp/dF2, d3 = d3logp/dF3) in closed form: what a Newton search for the posterior
+        mode needs (models.LaplaceGP)."""
+        raise NotImplementedError("%s defines no logp_derivatives(F, Y)" % type(self).__name__)
 
     def conditional_mean(self, F):
         raise NotImplementedError("%s defines no conditional_mean(F)" % type(self).__name__)
@@ -172,6 +178,25 @@ class Bernoulli(_NonGaussian):
             return _LogNdtr.apply(z)
         return torch.nn.functional.logsigmoid(z)             # = -softplus(-z), without softplus's linear threshold
 
+    def logp_derivatives(self, F, Y):
+        """the closed forms of csrc/laplace.hip.  Probit, with t = 2y - 1, z = t f and the hazard r = phi(z) / Phi(z) (erfcx for
+        z < 0): d1 = t r, W = r (z + r), d3 = t r ((z + r)(z + 2 r) - 1).  Logit, with e = exp(-|f|): d1 = t sigma(-z),
+        W = e / (1 + e)^2, d3 = W tanh(f / 2) = W sign(f) (1 - e) / (1 + e) -- nothing overflows."""
+        t = 2.0 * Y - 1.0
+        z = t * F
+        if self.link == "probit":
+            zn, zp = torch.clamp(z, max=0.0), torch.clamp(z, min=0.0)          # each branch on its own side only
+            neg = math.sqrt(2.0 / math.pi) / torch.special.erfcx(-zn * math.sqrt(0.5))
+            pos = torch.exp(-0.5 * zp * zp) * (1.0 / math.sqrt(2.0 * math.pi)) / (1.0 - 0.5 * torch.erfc(zp * math.sqrt(0.5)))
+            r = torch.where(z < 0.0, neg, pos)
+            zr = z + r
+            return torch.special.log_ndtr(z), t * r, r * zr, t * r * (zr * (zr + r) - 1.0)
+        e = torch.exp(-torch.abs(F))
+        q = 1.0 + e
+        W = e / (q * q)
+        return (torch.nn.functional.logsigmoid(z), t * (torch.where(z >= 0.0, e, torch.ones_like(e)) / q), W,
+                W * (torch.sign(F) * -torch.expm1(-torch.abs(F)) / q))
+
     def conditional_mean(self, F):
         return torch.special.ndtr(F) if self.link == "probit" else torch.sigmoid(F)
 
@@ -195,6 +220,10 @@ class Poisson(_NonGaussian):
 
     def logp(self, F, Y):
         return Y * F - torch.exp(F) - torch.lgamma(Y + 1.0)
+
+    def logp_derivatives(self, F, Y):
+        m = torch.exp(F)
+        return Y * F - m - torch.lgamma(Y + 1.0), Y - m, m, -m
 
     def conditional_mean(self, F):
         return torch.exp(F)

@@ -6,3 +6,4 @@ from ._multistart import multi_start_optimize  # noqa: F401
 from .sparse_gpr import SVGP, VFE  # noqa: F401
 from ._fitc import FITC  # noqa: F401
 from .dist_gpr import DistGPR  # noqa: F401
+from .laplace import LaplaceGP  # noqa: F401

@@ -721,6 +721,48 @@ int gpn_lik_expect(void* stream, int kind, const double* params, const double* f
                    double* work, int64_t work_bytes, double* value, double* g_mean, int64_t ldg, double* g_var,
                    double* g_params);
 
+/* ---- LaplaceGP (gptorch_amd/models/laplace.py): the exact GP under a log-concave non-Gaussian likelihood --------------
+ * With lp_i = log p(y_i | f_i), d1 = dlp/df, W = -d2lp/df2, d3 = d3lp/df3, s = sqrt(W): a Newton step of the mode search
+ * factors B = I + diag(s) K diag(s), and the gradient of the approximate evidence is sum_ij G_ij dK_ij/dtheta with an explicit
+ * G.  K is never stored: every entry below re-computes it tile by tile from the points (the assembly's arithmetic, so k_ij
+ * carries the bits gpn_kernel_matrix gives).  Every entry validates its arguments before any launch, adds up in a fixed order
+ * without atomics (the same call twice gives the same bits) and synchronises nothing.  All vectors have n entries. */
+/* value[0] = sum_i lp_i, d1, w, d3 [n] at f [n], y [n]; each output may be NULL.  kind: GPN_LIK_PROBIT / _LOGIT / _POISSON
+ * (GPN_LIK_STUDENT_T: GPN_E_UNSUPPORTED -- not log-concave).  Tail-stable closed forms (the point function of
+ * gpn_lik_expect): probit through the hazard r = phi / Phi (erfcx for z < 0), d1 = t r, W = r (z + r),
+ * d3 = t r ((z + r)(z + 2 r) - 1) with t = 2y - 1, z = t f; the logistic never overflows.
+ * work: work_bytes >= gpn_lik_derivs_work_bytes(n). */
+int64_t gpn_lik_derivs_work_bytes(int64_t n);
+int gpn_lik_derivs(void* stream, int kind, const double* f, const double* y, int64_t n, double* work, int64_t work_bytes,
+                   double* value, double* d1, double* w, double* d3);
+/* B_ij = delta_ij + s_i s_j k(x_i, x_j) into the entries on and below the diagonal of the factor buffer A (lda): the tile walk
+ * and staging of gpn_kernel_matrix(GPN_LOWER); nothing above the diagonal and nothing beyond column n is written. */
+int gpn_laplace_system(void* stream, int kind, const double* X, int64_t n, int d,
+                       const double* variance, const double* length_scales, int nls, const double* s, double* A, int64_t lda);
+/* out = K(X) v, matrix-free in plain fp64: one workgroup per lower 64 x 64 tile, which serves its rows and its mirror; the
+ * tile partials are added per row in a fixed order.  work: gpn_laplace_rows_work_bytes(n). */
+int64_t gpn_laplace_rows_work_bytes(int64_t n);
+int gpn_laplace_matvec(void* stream, int kind, const double* X, int64_t n, int d,
+                       const double* variance, const double* length_scales, int nls, const double* v, double* work, double* out);
+/* sigma_i = [(K^-1 + W)^-1]_ii = (1 / s_i) sum_j K_ij s_j Binv_ji, Binv = B^-1 read from its lower triangle (ldb).  The same
+ * sweep as gpn_laplace_matvec; s_i > 0.  work: gpn_laplace_rows_work_bytes(n). */
+int gpn_laplace_diag(void* stream, int kind, const double* X, int64_t n, int d,
+                     const double* variance, const double* length_scales, int nls, const double* s,
+                     const double* Binv, int64_t ldb, double* work, double* sigma);
+/* out[0] = sum_ij G_ij dK_ij/d variance, out[1 .. nls] = sum_ij G_ij dK_ij/d length_scales (CONSTRAINED values) with
+ * G = 1/2 a a^T - 1/2 diag(s) Binv diag(s) + 1/2 (u d1^T + d1 u^T), never materialised: the sweep of gpn_lml_grad over the
+ * lower tiles with the rank-one terms and the s_i s_j scaling in the tile epilogue.  work: gpn_laplace_grad_work_bytes(n, nls). */
+int64_t gpn_laplace_grad_work_bytes(int64_t n, int nls);
+int gpn_laplace_grad(void* stream, int kind, const double* X, int64_t n, int d,
+                     const double* variance, const double* length_scales, int nls, const double* s,
+                     const double* Binv, int64_t ldb, const double* a, const double* u, const double* d1,
+                     double* work, double* out);
+/* out [dy, ldo] = (L^-T alpha)^T for the alpha^T held in the extra rows of a factor buffer (gpn_potrf_lower): the
+ * back-substitution of gpn_lml_refine on its own.  lda = gpn_factor_ld(n, dy); work: gpn_backsub_work_bytes(n, dy). */
+int64_t gpn_backsub_work_bytes(int64_t n, int dy);
+int gpn_backsub(void* stream, const double* A, int64_t lda, const double* winv, int64_t n, int dy, double* work,
+                double* out, int64_t ldo);
+
 
 /* ---- optional launch profiler (bench.py's roofline legs) ---------------------- */
 /* While enabled, every contraction / assembly / gradient-sweep / leaf launch of this library is bracketed by two HIP events
