@@ -133,6 +133,23 @@ SIGNATURES = {
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "gpn_backsub_work_bytes": (c_int64, [c_int64, c_int]),
     "gpn_backsub": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64]),
+    # ... in lock step (models/_laplace_lockstep.py): `batch` models per launch
+    "gpn_lik_derivs_batched_work_bytes": (c_int64, [c_int64, c_int]),
+    "gpn_lik_derivs_batched": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64,
+                                       c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gpn_laplace_system_batched": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_int64]),
+    "gpn_laplace_rows_batched_work_bytes": (c_int64, [c_int64, c_int]),
+    "gpn_laplace_matvec_batched": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int,
+                                           c_void_p, c_int64, c_void_p, c_void_p]),
+    "gpn_laplace_diag_batched": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int,
+                                         c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
+    "gpn_laplace_grad_batched_work_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "gpn_laplace_grad_batched": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int,
+                                         c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    "gpn_backsub_batched_work_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "gpn_backsub_batched": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
+                                    c_int64, c_int64]),
 }
 LIK_PROBIT, LIK_LOGIT, LIK_POISSON, LIK_STUDENT_T = 0, 1, 2, 3   # include/gpnative.h GPN_LIK_*
 LIK_ROWS_PER_GROUP = 256                                        # GPN_LIK_ROWS_PER_GROUP

@@ -726,6 +726,115 @@ def backsub(f):
     return out
 
 
+# ---- the same in lock step (models/_laplace_lockstep.py): `batch` equal-shape models per launch.  X [n, d] shared or [batch, n, d],
+# variance [batch], length_scales [batch, nls], vectors stacked [batch, n]; every row of every result is bit-identical to the
+# single wrapper called on that model.  No host synchronisation.
+def _kargs_batched(X, variance, length_scales):
+    _req(X, variance, length_scales)
+    batch = int(variance.numel())
+    Xc, var, ls = _c(X.detach()), _c(variance.detach().reshape(batch)), _c(length_scales.detach().reshape(batch, -1))
+    n, d = Xc.shape[-2], Xc.shape[-1]
+    if Xc.dim() == 3 and Xc.shape[0] != batch:
+        raise ValueError("stacked points must be [batch, n, d] with batch = %d; got %s" % (batch, tuple(Xc.shape)))
+    return Xc, var, ls, batch, n, (batch, _ptr(Xc), 0 if Xc.dim() == 2 else n * d, n, d, _ptr(var), _ptr(ls), ls.shape[1])
+
+
+def _rows(t, batch, n, what):
+    _req(t)
+    if tuple(t.shape) != (batch, n):
+        raise ValueError("%s must be [%d, %d]; got %s" % (what, batch, n, tuple(t.shape)))
+    return _c(t.detach())
+
+
+def lik_derivs_batched(kind, f, y, want_value=True, want_d1=True, want_w=True, want_d3=True):
+    """gpn_lik_derivs_batched: lik_derivs for f [batch, n] and y [n] (shared) or [batch, n] -> (value [batch], d1, W, d3
+    [batch, n]); an output that is not wanted is None."""
+    batch, n = f.shape
+    f = _rows(f, batch, n, "f")
+    y = _vec(y, n, "y") if y.dim() == 1 else _rows(y, batch, n, "y")
+    dev = f.device
+    lib = _native.lib()
+    work = torch.empty(max(1, int(lib.gpn_lik_derivs_batched_work_bytes(n, batch)) // 8), dtype=torch.float64, device=dev)
+    outs = [torch.empty(batch, dtype=torch.float64, device=dev) if want_value else None]
+    outs += [torch.empty(batch, n, dtype=torch.float64, device=dev) if want else None for want in (want_d1, want_w, want_d3)]
+    st = lib.gpn_lik_derivs_batched(_stream(dev), kind, batch, _ptr(f), n, _ptr(y), 0 if y.dim() == 1 else n, n, _ptr(work), work.numel() * 8,
+                                    *[_ptr(o) for o in outs])
+    _native.check(st, "gpn_lik_derivs_batched")
+    return tuple(outs)
+
+
+def laplace_system_batched(kind, X, variance, length_scales, s, fb):
+    """gpn_laplace_system_batched: B_b = I + diag(s_b) K_b diag(s_b), on and below the diagonal, into the first `batch` slots of the
+    FactorBatch fb (batch = variance.numel() <= fb.batch)."""
+    Xc, var, ls, batch, n, args = _kargs_batched(X, variance, length_scales)
+    s = _rows(s, batch, n, "s")
+    if batch > fb.batch or n != fb.n:
+        raise ValueError("%d systems of %d rows do not fit a FactorBatch of %d x %d" % (batch, n, fb.batch, fb.n))
+    st = _native.lib().gpn_laplace_system_batched(_stream(Xc.device), KINDS[kind], *args, _ptr(s), n, _ptr(fb.A), fb.ld, fb.sA)
+    _native.check(st, "gpn_laplace_system_batched")
+    return fb
+
+
+def _rows_work_batched(n, batch, device, work):
+    need = max(1, int(_native.lib().gpn_laplace_rows_batched_work_bytes(n, batch)) // 8)
+    return work if (work is not None and work.numel() >= need and work.device == device) else torch.empty(need, dtype=torch.float64, device=device)
+
+
+def laplace_matvec_batched(kind, X, variance, length_scales, v, work=None):
+    """gpn_laplace_matvec_batched: K_b v_b [batch, n], matrix-free."""
+    Xc, var, ls, batch, n, args = _kargs_batched(X, variance, length_scales)
+    v = _rows(v, batch, n, "v")
+    work = _rows_work_batched(n, batch, Xc.device, work)
+    out = torch.empty(batch, n, dtype=torch.float64, device=Xc.device)
+    st = _native.lib().gpn_laplace_matvec_batched(_stream(Xc.device), KINDS[kind], *args, _ptr(v), n, _ptr(work), _ptr(out))
+    _native.check(st, "gpn_laplace_matvec_batched")
+    return out
+
+
+def laplace_diag_batched(kind, X, variance, length_scales, s, Binv, ldb, sB, work=None):
+    """gpn_laplace_diag_batched: diag((K_b^-1 + W_b)^-1) [batch, n]; Binv: a tensor (or device address) whose model b starts sB
+    doubles after model 0, leading dimension ldb, lower triangle read."""
+    Xc, var, ls, batch, n, args = _kargs_batched(X, variance, length_scales)
+    s = _rows(s, batch, n, "s")
+    work = _rows_work_batched(n, batch, Xc.device, work)
+    out = torch.empty(batch, n, dtype=torch.float64, device=Xc.device)
+    st = _native.lib().gpn_laplace_diag_batched(_stream(Xc.device), KINDS[kind], *args, _ptr(s), n, _addr(Binv), ldb, sB, _ptr(work), _ptr(out))
+    _native.check(st, "gpn_laplace_diag_batched")
+    return out
+
+
+def laplace_grad_batched(kind, X, variance, length_scales, s, Binv, ldb, sB, a, u, d1):
+    """gpn_laplace_grad_batched: [batch, 1 + nls], row b = laplace_grad of model b (Binv as in laplace_diag_batched)."""
+    Xc, var, ls, batch, n, args = _kargs_batched(X, variance, length_scales)
+    s, a, u, d1 = _rows(s, batch, n, "s"), _rows(a, batch, n, "a"), _rows(u, batch, n, "u"), _rows(d1, batch, n, "d1")
+    lib = _native.lib()
+    nls = ls.shape[1]
+    work = torch.empty(max(1, int(lib.gpn_laplace_grad_batched_work_bytes(n, nls, batch)) // 8), dtype=torch.float64, device=Xc.device)
+    out = torch.empty(batch, 1 + nls, dtype=torch.float64, device=Xc.device)
+    st = lib.gpn_laplace_grad_batched(_stream(Xc.device), KINDS[kind], *args, _ptr(s), _addr(Binv), ldb, sB, _ptr(a), _ptr(u), _ptr(d1), n,
+                                      _ptr(work), _ptr(out))
+    _native.check(st, "gpn_laplace_grad_batched")
+    return out
+
+
+def _addr(t):
+    return ctypes.c_void_p(t) if isinstance(t, int) else _ptr(t)
+
+
+def backsub_batched(fb, batch=None):
+    """gpn_backsub_batched: (L_b^-T alpha_b)^T [batch, e, n] for the extra rows of the first `batch` (default: all) factorised
+    slots of a FactorBatch."""
+    batch = fb.batch if batch is None else int(batch)
+    lib = _native.lib()
+    dev = fb.A.device
+    work = torch.empty(max(1, int(lib.gpn_backsub_batched_work_bytes(fb.n, fb.e, batch)) // 8), dtype=torch.float64, device=dev)
+    out = torch.empty(batch, fb.e, fb.n, dtype=torch.float64, device=dev)
+    st = lib.gpn_backsub_batched(_stream(dev), batch, _ptr(fb.A), fb.ld, fb.sA, _ptr(fb.winv), fb.sW, fb.n, fb.e, _ptr(work), _ptr(out),
+                                 fb.n, fb.e * fb.n)
+    _native.check(st, "gpn_backsub_batched")
+    return out
+
+
 def padded_like_factor(f, m):
     """zeroed [round_up(m,128), f.ld] buffer for right-hand sides of solve_right_lt."""
     return zeros(round_up(max(m, 1), LEAF), f.ld, f.device)

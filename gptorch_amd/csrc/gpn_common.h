@@ -100,6 +100,11 @@ int assemble_lower_saving(hipStream_t s, int kind, const double* X, int64_t n, i
 // I + diag(sc) K(X) diag(sc), the entries on and below the diagonal only (kmat.hip; gpn_laplace_system)
 int assemble_laplace_system(hipStream_t s, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
                             int nls, const double* sc, double* A, int64_t lda);
+// ... of `batch` models in one launch: points X + b sX (0: shared), variance[b], length_scales + b nls, sc + b sSc, slot A + b sA
+// (kmat.hip; gpn_laplace_system_batched)
+int assemble_laplace_system_batched(hipStream_t s, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
+                                    const double* variance, const double* length_scales, int nls, const double* sc, int64_t sSc,
+                                    double* A, int64_t lda, int64_t sA);
 // K(X_b) + noise_b I (lower tiles) + right-hand sides + info words of `batch` models (kmat.hip; gpn_lml_forward_batched)
 int assemble_batched(hipStream_t s, int kind, int batch, const double* X, int64_t sX, int64_t n, int d, const double* Y, int64_t sY,
                      const double* M, int64_t sM, int dy, const double* variance, const double* length_scales, int nls,

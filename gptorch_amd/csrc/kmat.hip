@@ -41,6 +41,7 @@ struct KmatArgs {
   double* K2 = nullptr;
   // gpn_laplace_system (LAPLACE instantiations only; symmetric lower): sqrt(W) of LaplaceGP's Newton step, n entries
   const double* sc = nullptr;
+  int64_t sSc = 0;    // ... of problem z at sc + z sSc (gpn_laplace_system_batched)
 };
 
 // LAPLACE (compile-time: the other instantiations are untouched): the entry becomes B_ij = delta_ij + s_i s_j k_ij, and only
@@ -58,6 +59,7 @@ __global__ __launch_bounds__(256) void kmat_kernel(KmatArgs p) {
     if (p.K2) p.K2 += z * p.sK;
     p.variance += z; p.ls += z * p.nls;
     if (p.noise) p.noise += z;
+    if constexpr (LAPLACE) p.sc += z * p.sSc;
   }
   if (p.n_of) nreal = p.n_of[blockIdx.z];
   int tj, ti;
@@ -259,6 +261,35 @@ int assemble_laplace_system(hipStream_t s, int kind, const double* X, int64_t n,
   const dim3 grid(tm * (tm + 1) / 2);
   int rec = -1;
   if (profile_on()) rec = profile_begin(s, 8.0 * (0.5 * n * (n + 1.0) + (double)n * d), PROF_KMAT);
+  switch (kind) {
+    case GPN_RBF: hipLaunchKernelGGL((kmat_kernel<GPN_RBF, true>), grid, dim3(256), 0, s, a); break;
+    case GPN_MATERN52: hipLaunchKernelGGL((kmat_kernel<GPN_MATERN52, true>), grid, dim3(256), 0, s, a); break;
+    case GPN_MATERN32: hipLaunchKernelGGL((kmat_kernel<GPN_MATERN32, true>), grid, dim3(256), 0, s, a); break;
+    case GPN_EXP: hipLaunchKernelGGL((kmat_kernel<GPN_EXP, true>), grid, dim3(256), 0, s, a); break;
+    case GPN_PERIODIC: hipLaunchKernelGGL((kmat_kernel<GPN_PERIODIC, true>), grid, dim3(256), 0, s, a); break;
+    default: return -2;
+  }
+  if (rec >= 0) profile_end(s, rec);
+  GPN_LAUNCH_CHECK();
+  return GPN_OK;
+}
+
+// assemble_laplace_system for `batch` models in one launch (gridDim.z): per model the same kernel, entry by entry
+int assemble_laplace_system_batched(hipStream_t s, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
+                                    const double* variance, const double* length_scales, int nls, const double* sc, int64_t sSc,
+                                    double* A, int64_t lda, int64_t sA) {
+  KmatArgs a;
+  a.X = X; a.X2 = X;
+  a.variance = variance; a.ls = length_scales; a.noise = nullptr; a.sc = sc; a.sSc = sSc;
+  a.K = A; a.ldk = lda;
+  a.n = (int)n; a.m = (int)n; a.d = d; a.nls = nls;
+  a.symmetric = 1; a.lower = 1;
+  a.vec_ok = ((lda & 1) == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0) && ((sA & 1) == 0);
+  a.sX = sX; a.sK = sA;
+  const unsigned tm = (unsigned)((n + KT - 1) / KT);
+  const dim3 grid(tm * (tm + 1) / 2, 1, (unsigned)batch);
+  int rec = -1;
+  if (profile_on()) rec = profile_begin(s, batch * 8.0 * (0.5 * n * (n + 1.0) + (double)n * d), PROF_KMAT);
   switch (kind) {
     case GPN_RBF: hipLaunchKernelGGL((kmat_kernel<GPN_RBF, true>), grid, dim3(256), 0, s, a); break;
     case GPN_MATERN52: hipLaunchKernelGGL((kmat_kernel<GPN_MATERN52, true>), grid, dim3(256), 0, s, a); break;

@@ -13,6 +13,9 @@
 //   lap_grad_kernel       the sweep of gpn_lml_grad (grad.hip, chunked form: any input dimension) with
 //                         G_ij = 1/2 a_i a_j - 1/2 s_i s_j Binv_ij + 1/2 (u_i d1_j + d1_i u_j) formed in the tile epilogue from the
 //                         four vectors (staged in LDS) and the lower triangle of Binv (read once, 16-byte loads).
+//   *_batched_kernel      the lock-step forms (gpn_*_batched; models/_laplace_lockstep.py): `batch` equal-shape models in one launch,
+//                         the model index on blockIdx.y, operands at a stride.  Each runs the single kernel's body (a device
+//                         function) after moving the operand pointers: per model the same arithmetic in the same order.
 // HBM traffic: MODE 1 and the gradient sweep read Binv's lower triangle once (4 n^2 bytes); MODE 0 reads the points only and is
 // bound by the fp64 exponentials.  Sums: a thread's own in a fixed order, then LDS in a fixed order, then the workspace in a
 // fixed order -- no atomics, the same call twice gives the same bits.
@@ -29,10 +32,12 @@ constexpr int LDC = 16;           // coordinates staged per pass (kmat.hip DC)
 constexpr int LD_THREADS = 256;   // points of a workgroup of lik_derivs_kernel, one per thread
 
 // ---- pointwise derivatives -------------------------------------------------------------------------------------------------
+// (the kernels' bodies are device functions: the single-model kernel runs them as they are, the lock-step kernel moves the
+//  operands to model blockIdx.y first -- one body, so a model's arithmetic does not depend on the entry point)
 template <int KIND>
-__global__ __launch_bounds__(LD_THREADS) void lik_derivs_kernel(const double* __restrict__ f, const double* __restrict__ y, int64_t n,
-                                                                double* __restrict__ partials, double* __restrict__ d1,
-                                                                double* __restrict__ w, double* __restrict__ d3) {
+__device__ __forceinline__ void lik_derivs_body(const double* __restrict__ f, const double* __restrict__ y, int64_t n,
+                                                double* __restrict__ partials, double* __restrict__ d1,
+                                                double* __restrict__ w, double* __restrict__ d3) {
   __shared__ double red[LD_THREADS / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t i = (int64_t)blockIdx.x * LD_THREADS + tid;
@@ -76,7 +81,28 @@ __global__ __launch_bounds__(LD_THREADS) void lik_derivs_kernel(const double* __
   if (tid == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+template <int KIND>
+__global__ __launch_bounds__(LD_THREADS) void lik_derivs_kernel(const double* __restrict__ f, const double* __restrict__ y, int64_t n,
+                                                                double* __restrict__ partials, double* __restrict__ d1,
+                                                                double* __restrict__ w, double* __restrict__ d3) {
+  lik_derivs_body<KIND>(f, y, n, partials, d1, w, d3);
+}
+
+// model blockIdx.y: f + b sf, y + b sy (0: shared), its workgroups' sums at partials + b gridDim.x, outputs [batch, n]
+template <int KIND>
+__global__ __launch_bounds__(LD_THREADS) void lik_derivs_batched_kernel(const double* __restrict__ f, int64_t sf, const double* __restrict__ y,
+                                                                        int64_t sy, int64_t n, double* __restrict__ partials,
+                                                                        double* __restrict__ d1, double* __restrict__ w,
+                                                                        double* __restrict__ d3) {
+  const int64_t b = blockIdx.y;
+  lik_derivs_body<KIND>(f + b * sf, y + b * sy, n, partials + b * gridDim.x, d1 ? d1 + b * n : nullptr, w ? w + b * n : nullptr,
+                        d3 ? d3 + b * n : nullptr);
+}
+
+// (one workgroup; the lock-step launch: workgroup b adds model b's `count` sums into value[b])
 __global__ __launch_bounds__(256) void lik_derivs_sum_kernel(const double* __restrict__ partials, int64_t count, double* __restrict__ value) {
+  partials += (int64_t)blockIdx.x * count;
+  value += blockIdx.x;
   __shared__ double red[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double a = 0.0;
@@ -104,6 +130,25 @@ struct LapArgs {
   double* work;
   int n, d, nls, tiles, nout;
 };
+
+// a lock-step launch: what separates model b's operands from model 0's, in doubles (X: 0 = shared points; the hyper-parameters
+// are consecutive: variance[b], ls + b nls)
+struct LapStrides {
+  int64_t X, vec, Binv, work;      // vec: every [n] vector (s, v, a, u, d1)
+};
+
+__device__ __forceinline__ void lap_model(LapArgs& p, const LapStrides& st, int64_t b) {
+  p.X += b * st.X;
+  p.variance += b;
+  p.ls += b * p.nls;
+  if (p.s) p.s += b * st.vec;
+  if (p.Binv) p.Binv += b * st.Binv;
+  if (p.v) p.v += b * st.vec;
+  if (p.a) p.a += b * st.vec;
+  if (p.u) p.u += b * st.vec;
+  if (p.d1) p.d1 += b * st.vec;
+  p.work += b * st.work;
+}
 
 // tile q of the row-major enumeration of the lower triangle (kmat.hip)
 __device__ __forceinline__ void lower_tile(int q, int& ti, int& tj) {
@@ -194,7 +239,7 @@ __device__ __forceinline__ void lap_load_binv(const LapArgs& p, int i0, int j0, 
 
 // ---- K v and diag((K^-1 + W)^-1) s ----------------------------------------------------------------------------------------------
 template <int KIND, int MODE>
-__global__ __launch_bounds__(256) void lap_rows_kernel(LapArgs p) {
+__device__ __forceinline__ void lap_rows_body(const LapArgs& p) {
   __shared__ __attribute__((aligned(16))) LapStage S;
   __shared__ double vrow[LT], vcol[LT];
   __shared__ double rpart[16][LT + 1], cpart[16][LT + 1];
@@ -254,11 +299,26 @@ __global__ __launch_bounds__(256) void lap_rows_kernel(LapArgs p) {
   }
 }
 
-// out_i = sum_J slot[I][J][i - 64 I], J ascending (divide != nullptr: ... / divide_i)
+template <int KIND, int MODE>
+__global__ __launch_bounds__(256) void lap_rows_kernel(LapArgs p) {
+  lap_rows_body<KIND, MODE>(p);
+}
+
+template <int KIND, int MODE>
+__global__ __launch_bounds__(256) void lap_rows_batched_kernel(LapArgs p, LapStrides st) {
+  lap_model(p, st, blockIdx.y);
+  lap_rows_body<KIND, MODE>(p);
+}
+
+// out_i = sum_J slot[I][J][i - 64 I], J ascending (divide != nullptr: ... / divide_i); model blockIdx.y of a lock-step launch has
+// its slots at work + b s_work, its divisors at divide + b s_div and its row of out at out + b n
 __global__ __launch_bounds__(256) void lap_gather_kernel(const double* __restrict__ work, int tiles, int64_t n, const double* __restrict__ divide,
-                                                         double* __restrict__ out) {
+                                                         double* __restrict__ out, int64_t s_work, int64_t s_div) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
+  work += blockIdx.y * s_work;
+  if (divide) divide += blockIdx.y * s_div;
+  out += blockIdx.y * n;
   const double* src = work + (i / LT) * (int64_t)tiles * LT + (i % LT);
   double sum = 0.0;
   for (int j = 0; j < tiles; ++j) sum += src[(int64_t)j * LT];
@@ -267,7 +327,7 @@ __global__ __launch_bounds__(256) void lap_gather_kernel(const double* __restric
 
 // ---- the evidence gradient ------------------------------------------------------------------------------------------------------
 template <int KIND>
-__global__ __launch_bounds__(256) void lap_grad_kernel(LapArgs p) {
+__device__ __forceinline__ void lap_grad_body(const LapArgs& p) {
   __shared__ __attribute__((aligned(16))) LapStage S;
   __shared__ double rows4[4][LT], cols4[4][LT];             // a, u, d1, s at the tile's rows and columns
   __shared__ double red[256];
@@ -358,10 +418,24 @@ __global__ __launch_bounds__(256) void lap_grad_kernel(LapArgs p) {
   }
 }
 
-// out[k] = sum over the tiles' partials, in a fixed order
+template <int KIND>
+__global__ __launch_bounds__(256) void lap_grad_kernel(LapArgs p) {
+  lap_grad_body<KIND>(p);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(256) void lap_grad_batched_kernel(LapArgs p, LapStrides st) {
+  lap_model(p, st, blockIdx.y);
+  lap_grad_body<KIND>(p);
+}
+
+// out[k] = sum over the tiles' partials, in a fixed order (model blockIdx.y of a lock-step launch: its nblocks x nout partials and
+// its row of out)
 __global__ __launch_bounds__(256) void lap_grad_reduce_kernel(const double* __restrict__ partial, int64_t nblocks, int nout, double* __restrict__ out) {
   __shared__ double red[256];
   const int k = blockIdx.x, tid = threadIdx.x;
+  partial += (int64_t)blockIdx.y * nblocks * nout;
+  out += (int64_t)blockIdx.y * nout;
   double s = 0.0;
   for (int64_t b = tid; b < nblocks; b += 256) s += partial[b * nout + k];
   red[tid] = s;
@@ -400,7 +474,45 @@ static int lap_rows_launch(hipStream_t s, int kind, const LapArgs& p, const doub
     default: hipLaunchKernelGGL((lap_rows_kernel<GPN_PERIODIC, MODE>), grid, dim3(256), 0, s, p); break;
   }
   GPN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(lap_gather_kernel, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p.work, p.tiles, (int64_t)p.n, divide, out);
+  hipLaunchKernelGGL(lap_gather_kernel, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p.work, p.tiles, (int64_t)p.n, divide, out,
+                     (int64_t)0, (int64_t)0);
+  GPN_LAUNCH_CHECK();
+  return GPN_OK;
+}
+
+constexpr int LAP_MAX_BATCH = 65535;      // the model index is a grid's y (z) dimension
+
+// ... and for the lock-step entry points: batch and sX follow kind (arguments 2 .. 10)
+static int lap_check_batched(int kind, int batch, const double* X, int64_t sX, int64_t n, int d, const double* variance,
+                             const double* length_scales, int nls) {
+  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;
+  if (batch < 1) return -3;
+  if (!X) return -4;
+  if (sX < 0) return -5;
+  if (n < 0 || n > 0x7fffffff) return -6;
+  if (d <= 0) return -7;
+  if (!variance) return -8;
+  if (!length_scales) return -9;
+  if (nls != 1 && nls != d) return -10;
+  return GPN_OK;
+}
+
+template <int MODE>
+static int lap_rows_launch_batched(hipStream_t s, int kind, int batch, const LapArgs& p, const LapStrides& st, const double* divide,
+                                   double* out) {
+  const int64_t t = p.tiles;
+  if (t * (t + 1) / 2 > 0x7fffffff || batch > LAP_MAX_BATCH) return GPN_E_UNSUPPORTED;
+  const dim3 grid((unsigned)(t * (t + 1) / 2), (unsigned)batch);
+  switch (kind) {
+    case GPN_RBF: hipLaunchKernelGGL((lap_rows_batched_kernel<GPN_RBF, MODE>), grid, dim3(256), 0, s, p, st); break;
+    case GPN_MATERN52: hipLaunchKernelGGL((lap_rows_batched_kernel<GPN_MATERN52, MODE>), grid, dim3(256), 0, s, p, st); break;
+    case GPN_MATERN32: hipLaunchKernelGGL((lap_rows_batched_kernel<GPN_MATERN32, MODE>), grid, dim3(256), 0, s, p, st); break;
+    case GPN_EXP: hipLaunchKernelGGL((lap_rows_batched_kernel<GPN_EXP, MODE>), grid, dim3(256), 0, s, p, st); break;
+    default: hipLaunchKernelGGL((lap_rows_batched_kernel<GPN_PERIODIC, MODE>), grid, dim3(256), 0, s, p, st); break;
+  }
+  GPN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lap_gather_kernel, dim3((unsigned)((p.n + 255) / 256), (unsigned)batch), dim3(256), 0, s, p.work, p.tiles, (int64_t)p.n,
+                     divide, out, st.work, st.vec);
   GPN_LAUNCH_CHECK();
   return GPN_OK;
 }
@@ -533,6 +645,151 @@ extern "C" int gpn_laplace_grad(void* stream, int kind, const double* X, int64_t
   if (rec >= 0) profile_end(s, rec);
   GPN_LAUNCH_CHECK();
   hipLaunchKernelGGL(lap_grad_reduce_kernel, dim3((unsigned)nout), dim3(256), 0, s, work, nblocks, nout, out);
+  GPN_LAUNCH_CHECK();
+  return GPN_OK;
+}
+
+// ---- the lock-step forms (models/_laplace_lockstep.py): the kernels above with the model index on blockIdx.y ---------------------
+extern "C" int64_t gpn_lik_derivs_batched_work_bytes(int64_t n, int batch) {
+  if (batch <= 0) return 0;
+  return batch * gpn_lik_derivs_work_bytes(n);
+}
+
+extern "C" int gpn_lik_derivs_batched(void* stream, int kind, int batch, const double* f, int64_t sf, const double* y, int64_t sy, int64_t n,
+                                      double* work, int64_t work_bytes, double* value, double* d1, double* w, double* d3) {
+  if (kind < GPN_LIK_PROBIT || kind > GPN_LIK_STUDENT_T) return -2;
+  if (kind == GPN_LIK_STUDENT_T) return GPN_E_UNSUPPORTED;
+  if (batch < 1) return -3;
+  if (!f) return -4;
+  if (sf < 0) return -5;
+  if (!y) return -6;
+  if (sy < 0) return -7;
+  if (n <= 0) return -8;
+  if (!work) return -9;
+  const int64_t blocks = (n + LD_THREADS - 1) / LD_THREADS;
+  if (blocks > 0x7fffffff || batch > LAP_MAX_BATCH) return GPN_E_UNSUPPORTED;
+  if (work_bytes < 8 * blocks * batch) return -10;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)blocks, (unsigned)batch), block(LD_THREADS);
+  switch (kind) {
+    case GPN_LIK_PROBIT: hipLaunchKernelGGL(lik_derivs_batched_kernel<GPN_LIK_PROBIT>, grid, block, 0, s, f, sf, y, sy, n, work, d1, w, d3); break;
+    case GPN_LIK_LOGIT: hipLaunchKernelGGL(lik_derivs_batched_kernel<GPN_LIK_LOGIT>, grid, block, 0, s, f, sf, y, sy, n, work, d1, w, d3); break;
+    default: hipLaunchKernelGGL(lik_derivs_batched_kernel<GPN_LIK_POISSON>, grid, block, 0, s, f, sf, y, sy, n, work, d1, w, d3); break;
+  }
+  GPN_LAUNCH_CHECK();
+  if (value) {
+    hipLaunchKernelGGL(lik_derivs_sum_kernel, dim3((unsigned)batch), dim3(256), 0, s, work, blocks, value);
+    GPN_LAUNCH_CHECK();
+  }
+  return GPN_OK;
+}
+
+extern "C" int gpn_laplace_system_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
+                                          const double* variance, const double* length_scales, int nls, const double* sc, int64_t ss,
+                                          double* A, int64_t lda, int64_t sA) {
+  const int rc = lap_check_batched(kind, batch, X, sX, n, d, variance, length_scales, nls);
+  if (rc != GPN_OK) return rc;
+  if (!sc) return -11;
+  if (ss < 0) return -12;
+  if (!A) return -13;
+  if (lda < n) return -14;
+  if (batch > 1 && sA < (n - 1) * lda + n) return -15;
+  if (batch > LAP_MAX_BATCH) return GPN_E_UNSUPPORTED;
+  if (n == 0) return GPN_OK;
+  return assemble_laplace_system_batched(static_cast<hipStream_t>(stream), kind, batch, X, sX, n, d, variance, length_scales, nls, sc, ss, A,
+                                         lda, sA);
+}
+
+extern "C" int64_t gpn_laplace_rows_batched_work_bytes(int64_t n, int batch) {
+  if (batch <= 0) return 0;
+  return batch * gpn_laplace_rows_work_bytes(n);
+}
+
+extern "C" int gpn_laplace_matvec_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
+                                          const double* variance, const double* length_scales, int nls, const double* v, int64_t sv,
+                                          double* work, double* out) {
+  const int rc = lap_check_batched(kind, batch, X, sX, n, d, variance, length_scales, nls);
+  if (rc != GPN_OK) return rc;
+  if (!v) return -11;
+  if (sv < 0) return -12;
+  if (!work) return -13;
+  if (!out) return -14;
+  if (n == 0) return GPN_OK;
+  LapArgs p = {};
+  p.X = X; p.variance = variance; p.ls = length_scales; p.v = v; p.work = work;
+  p.n = (int)n; p.d = d; p.nls = nls; p.tiles = (int)lap_tiles(n);
+  const LapStrides st = {sX, sv, 0, gpn_laplace_rows_work_bytes(n) / (int64_t)sizeof(double)};
+  return lap_rows_launch_batched<0>(static_cast<hipStream_t>(stream), kind, batch, p, st, nullptr, out);
+}
+
+extern "C" int gpn_laplace_diag_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
+                                        const double* variance, const double* length_scales, int nls, const double* sc, int64_t ss,
+                                        const double* Binv, int64_t ldb, int64_t sB, double* work, double* sigma) {
+  const int rc = lap_check_batched(kind, batch, X, sX, n, d, variance, length_scales, nls);
+  if (rc != GPN_OK) return rc;
+  if (!sc) return -11;
+  if (ss < 0) return -12;
+  if (!Binv) return -13;
+  if (ldb < n) return -14;
+  if (sB < 0) return -15;
+  if (!work) return -16;
+  if (!sigma) return -17;
+  if (n == 0) return GPN_OK;
+  LapArgs p = {};
+  p.X = X; p.variance = variance; p.ls = length_scales; p.s = sc; p.Binv = Binv; p.ldb = ldb; p.work = work;
+  p.n = (int)n; p.d = d; p.nls = nls; p.tiles = (int)lap_tiles(n);
+  const LapStrides st = {sX, ss, sB, gpn_laplace_rows_work_bytes(n) / (int64_t)sizeof(double)};
+  return lap_rows_launch_batched<1>(static_cast<hipStream_t>(stream), kind, batch, p, st, sc, sigma);
+}
+
+extern "C" int64_t gpn_laplace_grad_batched_work_bytes(int64_t n, int nls, int batch) {
+  if (batch <= 0) return 0;
+  return batch * gpn_laplace_grad_work_bytes(n, nls);
+}
+
+extern "C" int gpn_laplace_grad_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
+                                        const double* variance, const double* length_scales, int nls, const double* sc,
+                                        const double* Binv, int64_t ldb, int64_t sB, const double* a, const double* u, const double* d1,
+                                        int64_t sv, double* work, double* out) {
+  const int rc = lap_check_batched(kind, batch, X, sX, n, d, variance, length_scales, nls);
+  if (rc != GPN_OK) return rc;
+  if (!sc) return -11;
+  if (!Binv) return -12;
+  if (ldb < n) return -13;
+  if (sB < 0) return -14;
+  if (!a) return -15;
+  if (!u) return -16;
+  if (!d1) return -17;
+  if (sv < 0) return -18;
+  if (!work) return -19;
+  if (!out) return -20;
+  if (batch > LAP_MAX_BATCH) return GPN_E_UNSUPPORTED;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int nout = 1 + nls;
+  if (n == 0) {
+    GPN_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)batch * nout * sizeof(double), s));
+    return GPN_OK;
+  }
+  LapArgs p = {};
+  p.X = X; p.variance = variance; p.ls = length_scales; p.s = sc; p.Binv = Binv; p.ldb = ldb;
+  p.a = a; p.u = u; p.d1 = d1; p.work = work;
+  p.n = (int)n; p.d = d; p.nls = nls; p.tiles = (int)lap_tiles(n); p.nout = nout;
+  const int64_t t = p.tiles, nblocks = t * (t + 1) / 2;
+  if (nblocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
+  const LapStrides st = {sX, sv, sB, nblocks * nout};
+  const dim3 grid((unsigned)nblocks, (unsigned)batch);
+  int rec = -1;
+  if (profile_on()) rec = profile_begin(s, batch * 8.0 * (0.5 * n * (n + 1.0) + (double)n * d), PROF_GRAD);
+  switch (kind) {
+    case GPN_RBF: hipLaunchKernelGGL(lap_grad_batched_kernel<GPN_RBF>, grid, dim3(256), 0, s, p, st); break;
+    case GPN_MATERN52: hipLaunchKernelGGL(lap_grad_batched_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, p, st); break;
+    case GPN_MATERN32: hipLaunchKernelGGL(lap_grad_batched_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, p, st); break;
+    case GPN_EXP: hipLaunchKernelGGL(lap_grad_batched_kernel<GPN_EXP>, grid, dim3(256), 0, s, p, st); break;
+    default: hipLaunchKernelGGL(lap_grad_batched_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, p, st); break;
+  }
+  if (rec >= 0) profile_end(s, rec);
+  GPN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lap_grad_reduce_kernel, dim3((unsigned)nout, (unsigned)batch), dim3(256), 0, s, work, nblocks, nout, out);
   GPN_LAUNCH_CHECK();
   return GPN_OK;
 }

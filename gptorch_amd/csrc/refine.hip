@@ -33,9 +33,12 @@ constexpr int BS_COLS = 128;  // columns per workgroup of the back-substitution 
 
 // s <- alpha^T (the first n entries of the factor buffer's extra rows; what is right of them is the corner that
 // accumulated -alpha alpha^T), zero padded to lds
-__global__ void refine_init_kernel(const double* A, int64_t lda, int64_t n, int dy, double* s, int64_t lds) {
+// (factor slot blockIdx.y of a lock-step launch: A + b sA, s + b sS; gpn_backsub_batched)
+__global__ void refine_init_kernel(const double* A, int64_t lda, int64_t n, int dy, double* s, int64_t lds, int64_t sA = 0, int64_t sS = 0) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= lds) return;
+  A += blockIdx.y * sA;
+  s += blockIdx.y * sS;
   for (int c = 0; c < dy; ++c) s[(int64_t)c * lds + i] = i < n ? A[(n + c) * lda + i] : 0.0;
 }
 
@@ -51,10 +54,16 @@ __global__ void refine_init_kernel(const double* A, int64_t lda, int64_t n, int 
 template <int NRHS>
 __global__ __launch_bounds__(256) void backsub_step_kernel(const double* __restrict__ A, int64_t lda, const double* __restrict__ winv,
                                                            int k, int nb, int64_t n, int dy, int c0, double* __restrict__ s,
-                                                           double* __restrict__ a, int64_t lds) {
+                                                           double* __restrict__ a, int64_t lds, int64_t sA = 0, int64_t sW = 0,
+                                                           int64_t sS = 0) {
   __shared__ double ak[NRHS][LEAF];
   __shared__ double part[4][NRHS][BS_COLS];
   __shared__ double sj[NRHS][LEAF];
+  // factor slot blockIdx.y of a lock-step launch (gpn_backsub_batched): A + b sA, winv + b sW, s and a + b sS; nothing else differs
+  A += blockIdx.y * sA;
+  winv += blockIdx.y * sW;
+  s += blockIdx.y * sS;
+  a += blockIdx.y * sS;
   const int t = threadIdx.x;
   const int nc = min(NRHS, dy - c0);
   const int jb = k - 1 - (int)blockIdx.x;                  // my column block (workgroup 0: block k-1)
@@ -878,5 +887,51 @@ extern "C" int gpn_backsub(void* stream, const double* A, int64_t lda, const dou
   if (rc != GPN_OK) return rc;
   GPN_HIP_CHECK(hipMemcpy2DAsync(out, ldo * sizeof(double), work + L.a, L.lds * sizeof(double), n * sizeof(double), dy,
                                  hipMemcpyDeviceToDevice, s));
+  return GPN_OK;
+}
+
+// gpn_backsub for the `batch` factor slots of a lock-step factorisation: backsub_step_kernel, one launch per 128-column block with
+// the slots on blockIdx.y (bit-identical to the persistent kernel gpn_backsub runs, see above, and without its waiting between
+// workgroups).  work: per slot the s and a regions of gpn_backsub's layout, one slot's block after the other.
+extern "C" int64_t gpn_backsub_batched_work_bytes(int64_t n, int dy, int batch) {
+  if (batch <= 0) return 0;
+  return batch * gpn_backsub_work_bytes(n, dy);
+}
+
+extern "C" int gpn_backsub_batched(void* stream, int batch, const double* A, int64_t lda, int64_t sA, const double* winv, int64_t sW,
+                                   int64_t n, int dy, double* work, double* out, int64_t ldo, int64_t so) {
+  if (batch < 1) return -2;
+  if (!A) return -3;
+  if (n < 0) return -8;
+  if (dy <= 0) return -9;
+  if (lda != gpn_factor_ld(n, dy)) return -4;
+  if (batch > 1 && sA < (n + dy) * lda) return -5;
+  if (!winv) return -6;
+  if (batch > 1 && sW < gpn_winv_bytes(n) / (int64_t)sizeof(double)) return -7;
+  if (!work) return -10;
+  if (!out) return -11;
+  if (ldo < n) return -12;
+  if (batch > 1 && so < (dy - 1) * ldo + n) return -13;
+  if (batch > 65535) return GPN_E_UNSUPPORTED;
+  if (n == 0) return GPN_OK;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const RefineLayout L = refine_layout(n, dy);
+  const int64_t sS = 2 * (int64_t)dy * L.lds;                // one slot's s and a regions
+  double* sv = work + L.s;
+  double* av = work + L.a;
+  hipLaunchKernelGGL(refine_init_kernel, dim3((unsigned)((L.lds + 255) / 256), (unsigned)batch), dim3(256), 0, s, A, lda, n, dy, sv, L.lds, sA, sS);
+  GPN_LAUNCH_CHECK();
+  const int nb = (int)((n + LEAF - 1) / LEAF);
+  for (int c0 = 0; c0 < dy; c0 += (dy == 1 ? 1 : RDY))
+    for (int k = nb; k >= 1; --k) {
+      const dim3 grid((unsigned)(k == nb ? 1 : k), (unsigned)batch);
+      if (dy == 1) hipLaunchKernelGGL(backsub_step_kernel<1>, grid, dim3(256), 0, s, A, lda, winv, k, nb, n, dy, c0, sv, av, L.lds, sA, sW, sS);
+      else hipLaunchKernelGGL(backsub_step_kernel<RDY>, grid, dim3(256), 0, s, A, lda, winv, k, nb, n, dy, c0, sv, av, L.lds, sA, sW, sS);
+    }
+  GPN_LAUNCH_CHECK();
+  const int64_t dpitch = batch > 1 ? so : ldo;               // (one slot: any pitch of at least a row)
+  for (int c = 0; c < dy; ++c)                                // row c of every slot: one strided copy over the slots
+    GPN_HIP_CHECK(hipMemcpy2DAsync(out + (int64_t)c * ldo, dpitch * sizeof(double), av + (int64_t)c * L.lds, sS * sizeof(double),
+                                   n * sizeof(double), batch, hipMemcpyDeviceToDevice, s));
   return GPN_OK;
 }

@@ -232,6 +232,56 @@ def _vfe_group_bound(ms, key, differentiable):
     return _vfe_lockstep.BatchedVFEBound.apply(var, ls, s2, Z, key[1], X, Y)
 
 
+def _laplace_key(m):
+    k = m.kernel
+    return ("laplace", k._kind, m._lik_kind, tuple(m.X.shape), int(k.length_scales.numel()), m.X.device)
+
+
+def _laplace_groups(models):
+    """[(key, indices)] of the LaplaceGP models that can share one lock-step evaluation (_laplace_lockstep.BatchedLaplaceEvidence):
+    LaplaceGP's own log_likelihood over points on the GPU, grouped by (kernel kind, likelihood kind, X's shape, number of length
+    scales, device) and split into chunks that fit the device's free memory; singletons stay sequential.
+    key = ("laplace", kind, likelihood kind, X's shape, number of length scales, device)."""
+    from . import _laplace_lockstep
+    from .laplace import LaplaceGP
+    groups = {}
+    for i, m in enumerate(models):
+        if not isinstance(m, LaplaceGP) or type(m).log_likelihood is not LaplaceGP.log_likelihood:
+            continue
+        if not (isinstance(m.X, torch.Tensor) and m.X.is_cuda) or not _laplace_lockstep.supported(m.X.shape[0]):
+            continue
+        groups.setdefault(_laplace_key(m), []).append(i)
+    out = []
+    for key, g in groups.items():
+        out += _chunks(key, g, _capacity(_laplace_lockstep.per_model_bytes(key[3][0]), key[5], held=_held_bytes()))
+    return out
+
+
+def _laplace_group_inputs(ms, differentiable):
+    """(X, Y, variance [B], length scales [B, nls], [m_b = mean_function(X_b)]) of one _laplace_groups group: X and Y shared when
+    every model holds the same tensors (restarts on one data set), else stacked"""
+    m0 = ms[0]
+    same_x = all(m.X.data_ptr() == m0.X.data_ptr() for m in ms)
+    same_y = same_x and all(m.Y.data_ptr() == m0.Y.data_ptr() for m in ms)
+    X = m0.X if same_x else torch.stack([m.X for m in ms])
+    Y = m0.Y if same_y else torch.stack([m.Y for m in ms])
+    var = _stacked([m.kernel.variance for m in ms], differentiable).reshape(len(ms))
+    ls = _stacked([m.kernel.length_scales for m in ms], differentiable).reshape(len(ms), -1)
+    if differentiable:
+        means = [m.mean_function(m.X) for m in ms]
+    else:
+        with torch.no_grad():
+            means = [m.mean_function(m.X) for m in ms]
+    return X, Y, var, ls, means
+
+
+def _laplace_group_evidence(ms, key, differentiable):
+    """the lock-step evidences [B] of one _laplace_groups group (autograd-connected to every model's Params when differentiable)"""
+    from . import _laplace_lockstep
+    X, Y, var, ls, means = _laplace_group_inputs(ms, differentiable)
+    return _laplace_lockstep.BatchedLaplaceEvidence.apply(X, Y, var, ls, key[1], key[2], ms, _batch_holder((key, len(ms))), *means)
+
+
 def _group_data(ms, differentiable=False, key=None):
     """(X, R, n_of) of a lock-step group: shared [n, d] / [n, dy] when every model holds the same tensors (restarts on one data
     set), else stacked [B, ...].  differentiable: R keeps the autograd graph of trainable mean functions.
@@ -319,6 +369,10 @@ def batched_log_likelihood(models, streams=None):
             elbo = _vfe_group_bound([models[i] for i in g], key, differentiable=False)
             for b, i in enumerate(g):
                 out[i] = elbo[b]                                             # (VFE.log_likelihood returns a 0-dim tensor)
+        for key, g in _laplace_groups(models):
+            ev = _laplace_group_evidence([models[i] for i in g], key, differentiable=False)
+            for b, i in enumerate(g):
+                out[i] = ev[b:b + 1]                                         # (LaplaceGP.log_likelihood returns a (1,) tensor)
         for i, m in enumerate(models):
             if out[i] is None:
                 out[i] = m.log_likelihood()
@@ -347,6 +401,21 @@ def batched_factorise(models):
                 if int(info[b]) == 0:
                     m._seed_cached_state(key.kind, m.X, fb.factor(b))
                     seeded += 1
+        for key, g in _laplace_groups(models):
+            # LaplaceGP folds: the mode searches in lock step into buffers of their own; every model's prediction cache gets its
+            # mode, with a^ in the factor's extra row as LaplaceGP._mode_for_predict leaves it
+            from . import _laplace_lockstep
+            ms = [models[i] for i in g]
+            X, Y, var, ls, means = _laplace_group_inputs(ms, differentiable=False)
+            n = X.shape[-2]
+            modes = _laplace_lockstep.find_modes(key[1], key[2], X, Y.reshape(n) if Y.dim() == 2 else Y.reshape(len(ms), n),
+                                                 torch.stack([mu.reshape(n) for mu in means]), var, ls, [m._start(n) for m in ms],
+                                                 [m.newton_tol for m in ms], [m.max_newton_iter for m in ms])
+            for m, mode in zip(ms, modes):
+                m._remember(mode)
+                mode.factor.A[n, :n] = mode.a
+                m._seed_cached_state(("laplace", key[1]), m.X, mode)
+                seeded += 1
     return seeded
 
 
@@ -355,14 +424,15 @@ def _has_priors(ms):
 
 
 def _plan_groups(models):
-    """the grouping of batched_loss_and_grad for a list of models: [(lock-step groups), (expression groups), (sparse groups)] with each
-    group's "has priors" flag.  Shapes, kernels and priors do not change while a search runs: multi_start_optimize plans ONCE and
-    hands the plan to every iteration (the grouping walks every model's parameters and, for composite kernels, rebuilds their
+    """the grouping of batched_loss_and_grad for a list of models: [(lock-step groups), (expression groups), (sparse groups),
+    (LaplaceGP groups)] with each group's "has priors" flag.  Shapes, kernels and priors do not change while a search runs:
+    multi_start_optimize plans ONCE and hands the plan to every iteration (the grouping walks every model's parameters and, for composite kernels, rebuilds their
     expression programs: host time that a small-N iteration would spend several times over)."""
     _place_all(models)
     return ([(key, g, _has_priors([models[i] for i in g])) for key, g in _lockstep_groups(models)],
             [(key, g, progs, _has_priors([models[i] for i in g])) for key, g, progs in _expression_groups(models)],
-            [(key, g, _has_priors([models[i] for i in g])) for key, g in _vfe_groups(models)])
+            [(key, g, _has_priors([models[i] for i in g])) for key, g in _vfe_groups(models)],
+            [(key, g, _has_priors([models[i] for i in g])) for key, g in _laplace_groups(models)])
 
 
 def _group_loss_and_grad(value, ms, g, priors, out, keepdim):
@@ -393,7 +463,9 @@ def batched_loss_and_grad(models, _plan=None):
     transforms and their chain rule are one small launch per parameter kind.  Each model's loss AND gradients are
     BIT-IDENTICAL to its own `loss(); backward()`; a model whose factorisation fails is replayed alone through the jitter
     ladder; parameters with priors add their model's own log_prior() (model.py:158-197); sizes that refine the quadratic
-    form refine it per model.  Composite / dense-K kernels and singletons take the sequential path."""
+    form refine it per model.  Composite / dense-K kernels and singletons take the sequential path.  Equal-shape LaplaceGP models
+    run their mode searches, evidences and closed-form gradients in lock step too (_laplace_groups, models/_laplace_lockstep.py),
+    each model's loss, gradients, warm-start mode and newton_stats bit-identical to its own evaluation."""
     plan = _plan if _plan is not None else _plan_groups(models)
     out = [None] * len(models)
     for key, g, priors in plan[0]:
@@ -417,6 +489,10 @@ def batched_loss_and_grad(models, _plan=None):
         # sparse models of one shape (sparse_gpr.py:108-153 in a multi-start search over inducing points / hyper-parameters)
         ms = [models[i] for i in g]
         _group_loss_and_grad(_vfe_group_bound(ms, key, differentiable=True), ms, g, priors, out, False)
+    for key, g, priors in plan[3]:
+        # LaplaceGP restarts / folds of one shape: the Newton searches, evidences and closed-form gradients in lock step
+        ms = [models[i] for i in g]
+        _group_loss_and_grad(_laplace_group_evidence(ms, key, differentiable=True), ms, g, priors, out, True)
     for i, m in enumerate(models):
         if out[i] is None:
             loss = m.loss()

@@ -35,8 +35,12 @@ Prediction: mean_f = m(x*) + K(x*, X) a^, cov_f = K(x*, x*) - V^T V with V = L^-
 marginals to likelihood.predict_mean_variance (diag=False raises: a non-Gaussian likelihood has no predictive covariance).
 The mode, s and the factor are kept between predictions (GPModel._cached_state).
 
-Out of scope: composite kernels, dy > 1, Student-t (not log-concave: W may be negative and B indefinite), lock-step restarts
-and multi_start_optimize, optimize(capture=True) (the search reads the host), DistGPR, expectation propagation.
+Restarts and folds: equal-shape LaplaceGP models handed to batched_log_likelihood / batched_loss_and_grad / multi_start_optimize /
+batched_factorise run their searches, evidences, gradients and prediction states in LOCK STEP (models/_laplace_lockstep.py), every
+number bit-identical to the model's own evaluation here.
+
+Out of scope: composite kernels, dy > 1, Student-t (not log-concave: W may be negative and B indefinite), ragged (unequal-N)
+lock-step groups, optimize(capture=True) (the search reads the host), DistGPR, expectation propagation.
 """
 import sys
 
@@ -141,6 +145,20 @@ def _solve_b(factor, w):
     return _ops.backsub(factor)[0]
 
 
+def _evidence_gradients(kind, X, var, ls, mode):
+    """the closed form of the module docstring at one mode -> (g [1 + nls] = dlog q/d(variance, length_scales), u [n])"""
+    f = mode.factor
+    if f.generation != mode.generation:
+        # the model's reusable buffer was refactorised by a later forward: rebuild this node's factor privately
+        f = _ops.Factor(f.n, 1, f.device)
+        _factor_system(kind, X, var, ls, mode.s, f)
+    Binv = _backward._kinv_lower(f, _backward._upper_inverse(f))
+    sigma = _ops.laplace_diag(kind, X, var, ls, mode.s, Binv)
+    s2 = 0.5 * sigma * mode.d3
+    u = s2 - mode.s * _solve_b(f, mode.s * _ops.laplace_matvec(kind, X, var, ls, s2))
+    return _ops.laplace_grad(kind, X, var, ls, mode.s, Binv, mode.a, u, mode.d1), u
+
+
 class LaplaceEvidence(torch.autograd.Function):
     """log q(y | theta) as ONE autograd node: the Newton loop in the forward, the closed form of the module docstring in the
     backward.  Inputs: the points, the targets [n, 1], m = mean_function(X) [n, 1], the CONSTRAINED variance and
@@ -163,17 +181,8 @@ class LaplaceEvidence(torch.autograd.Function):
         X, variance, length_scales = ctx.saved_tensors
         kind, mode = ctx.kind, ctx.mode
         var, ls = variance.detach(), length_scales.detach()
-        f = mode.factor
-        if f.generation != mode.generation:
-            # the model's reusable buffer was refactorised by a later forward: rebuild this node's factor privately
-            f = _ops.Factor(f.n, 1, f.device)
-            _factor_system(kind, X, var, ls, mode.s, f)
-        n = f.n
-        Binv = _backward._kinv_lower(f, _backward._upper_inverse(f))
-        sigma = _ops.laplace_diag(kind, X, var, ls, mode.s, Binv)
-        s2 = 0.5 * sigma * mode.d3
-        u = s2 - mode.s * _solve_b(f, mode.s * _ops.laplace_matvec(kind, X, var, ls, s2))
-        g = _ops.laplace_grad(kind, X, var, ls, mode.s, Binv, mode.a, u, mode.d1)
+        n = mode.factor.n
+        g, u = _evidence_gradients(kind, X, var, ls, mode)
         go = grad_out.reshape(())
         nls = length_scales.numel()
         return (None, None, (go * (mode.d1 + u)).reshape(n, 1) if ctx.needs_input_grad[2] else None,

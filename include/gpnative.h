@@ -763,6 +763,47 @@ int64_t gpn_backsub_work_bytes(int64_t n, int dy);
 int gpn_backsub(void* stream, const double* A, int64_t lda, const double* winv, int64_t n, int dy, double* work,
                 double* out, int64_t ldo);
 
+/* ---- LaplaceGP in lock step (gptorch_amd/models/_laplace_lockstep.py): the entry points above for `batch` equal-shape models,
+ * ONE launch each with the model index on a grid dimension.  Model b reads its points at X + b*sX (sX = 0: shared points, as
+ * gpn_kernel_matrix_batched), variance[b], length_scales + b*nls and its vectors at the given strides (in doubles); per model
+ * the arithmetic and the order of every sum are the single entry point's, so each model's results are BIT-IDENTICAL to `batch`
+ * single calls.  Arguments are validated in order before any launch (-k: the k-th argument, the stream being the first);
+ * batch > 65535 (a grid dimension): GPN_E_UNSUPPORTED.  Nothing is synchronised or read back. */
+/* value[b], d1 / w / d3 [batch, n] (row b at b*n; each output may be NULL) at f + b*sf, y + b*sy (sy = 0: shared targets).
+ * work: work_bytes >= gpn_lik_derivs_batched_work_bytes(n, batch) = batch * gpn_lik_derivs_work_bytes(n). */
+int64_t gpn_lik_derivs_batched_work_bytes(int64_t n, int batch);
+int gpn_lik_derivs_batched(void* stream, int kind, int batch, const double* f, int64_t sf, const double* y, int64_t sy, int64_t n,
+                           double* work, int64_t work_bytes, double* value, double* d1, double* w, double* d3);
+/* B_b = I + diag(s_b) K_b diag(s_b), s_b = s + b*ss, into the entries on and below the diagonal of factor slot A + b*sA (the
+ * layout of gpn_potrf_lower_batched); nothing outside a slot's lower triangle is written. */
+int gpn_laplace_system_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
+                               const double* variance, const double* length_scales, int nls, const double* s, int64_t ss,
+                               double* A, int64_t lda, int64_t sA);
+/* out [batch, n]: row b = K_b v_b, v_b = v + b*sv.  work: gpn_laplace_rows_batched_work_bytes(n, batch)
+ * = batch * gpn_laplace_rows_work_bytes(n). */
+int64_t gpn_laplace_rows_batched_work_bytes(int64_t n, int batch);
+int gpn_laplace_matvec_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
+                               const double* variance, const double* length_scales, int nls, const double* v, int64_t sv,
+                               double* work, double* out);
+/* sigma [batch, n]: row b = gpn_laplace_diag of model b with s_b = s + b*ss and Binv_b = Binv + b*sB (leading dimension ldb).
+ * work: gpn_laplace_rows_batched_work_bytes(n, batch). */
+int gpn_laplace_diag_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
+                             const double* variance, const double* length_scales, int nls, const double* s, int64_t ss,
+                             const double* Binv, int64_t ldb, int64_t sB, double* work, double* sigma);
+/* out [batch, 1 + nls]: row b = gpn_laplace_grad of model b; s, a, u, d1 all at stride sv, Binv_b = Binv + b*sB.
+ * work: gpn_laplace_grad_batched_work_bytes(n, nls, batch) = batch * gpn_laplace_grad_work_bytes(n, nls). */
+int64_t gpn_laplace_grad_batched_work_bytes(int64_t n, int nls, int batch);
+int gpn_laplace_grad_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
+                             const double* variance, const double* length_scales, int nls, const double* s,
+                             const double* Binv, int64_t ldb, int64_t sB, const double* a, const double* u, const double* d1,
+                             int64_t sv, double* work, double* out);
+/* out + b*so [dy, ldo] = (L_b^-T alpha_b)^T for every factor slot A + b*sA, winv + b*sW of a gpn_potrf_lower_batched call: one
+ * launch per 128-column block with the models on a grid dimension and no waiting between workgroups; per model bit-identical to
+ * gpn_backsub.  work: gpn_backsub_batched_work_bytes(n, dy, batch) = batch * gpn_backsub_work_bytes(n, dy). */
+int64_t gpn_backsub_batched_work_bytes(int64_t n, int dy, int batch);
+int gpn_backsub_batched(void* stream, int batch, const double* A, int64_t lda, int64_t sA, const double* winv, int64_t sW,
+                        int64_t n, int dy, double* work, double* out, int64_t ldo, int64_t so);
+
 
 /* ---- optional launch profiler (bench.py's roofline legs) ---------------------- */
 /* While enabled, every contraction / assembly / gradient-sweep / leaf launch of this library is bracketed by two HIP events
