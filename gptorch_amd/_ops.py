@@ -670,8 +670,8 @@ def laplace_system(kind, X, variance, length_scales, s, out, ldo):
     return out
 
 
-def _rows_work(n, device, work):
-    need = max(1, int(_native.lib().gpn_laplace_rows_work_bytes(n)) // 8)
+def _rows_work(n, device, work, batch=1):
+    need = max(1, batch * int(_native.lib().gpn_laplace_rows_work_bytes(n)) // 8)      # (= gpn_laplace_rows_batched_work_bytes(n, batch))
     return work if (work is not None and work.numel() >= need and work.device == device) else torch.empty(need, dtype=torch.float64, device=device)
 
 
@@ -775,16 +775,11 @@ def laplace_system_batched(kind, X, variance, length_scales, s, fb):
     return fb
 
 
-def _rows_work_batched(n, batch, device, work):
-    need = max(1, int(_native.lib().gpn_laplace_rows_batched_work_bytes(n, batch)) // 8)
-    return work if (work is not None and work.numel() >= need and work.device == device) else torch.empty(need, dtype=torch.float64, device=device)
-
-
 def laplace_matvec_batched(kind, X, variance, length_scales, v, work=None):
     """gpn_laplace_matvec_batched: K_b v_b [batch, n], matrix-free."""
     Xc, var, ls, batch, n, args = _kargs_batched(X, variance, length_scales)
     v = _rows(v, batch, n, "v")
-    work = _rows_work_batched(n, batch, Xc.device, work)
+    work = _rows_work(n, Xc.device, work, batch)
     out = torch.empty(batch, n, dtype=torch.float64, device=Xc.device)
     st = _native.lib().gpn_laplace_matvec_batched(_stream(Xc.device), KINDS[kind], *args, _ptr(v), n, _ptr(work), _ptr(out))
     _native.check(st, "gpn_laplace_matvec_batched")
@@ -796,7 +791,7 @@ def laplace_diag_batched(kind, X, variance, length_scales, s, Binv, ldb, sB, wor
     doubles after model 0, leading dimension ldb, lower triangle read."""
     Xc, var, ls, batch, n, args = _kargs_batched(X, variance, length_scales)
     s = _rows(s, batch, n, "s")
-    work = _rows_work_batched(n, batch, Xc.device, work)
+    work = _rows_work(n, Xc.device, work, batch)
     out = torch.empty(batch, n, dtype=torch.float64, device=Xc.device)
     st = _native.lib().gpn_laplace_diag_batched(_stream(Xc.device), KINDS[kind], *args, _ptr(s), n, _addr(Binv), ldb, sB, _ptr(work), _ptr(out))
     _native.check(st, "gpn_laplace_diag_batched")

@@ -13,9 +13,10 @@
 //   lap_grad_kernel       the sweep of gpn_lml_grad (grad.hip, chunked form: any input dimension) with
 //                         G_ij = 1/2 a_i a_j - 1/2 s_i s_j Binv_ij + 1/2 (u_i d1_j + d1_i u_j) formed in the tile epilogue from the
 //                         four vectors (staged in LDS) and the lower triangle of Binv (read once, 16-byte loads).
-//   *_batched_kernel      the lock-step forms (gpn_*_batched; models/_laplace_lockstep.py): `batch` equal-shape models in one launch,
-//                         the model index on blockIdx.y, operands at a stride.  Each runs the single kernel's body (a device
-//                         function) after moving the operand pointers: per model the same arithmetic in the same order.
+// One kernel per operation: every kernel takes `batch` equal-shape models in one launch, the model index on blockIdx.y and model
+// b's operands at a stride (lap_model; sf, sy).  The lock-step entry points (gpn_*_batched; models/_laplace_lockstep.py) launch
+// gridDim.y = batch; a single entry point is its lock-step twin at batch = 1 with every stride 0, so a model's arithmetic and the
+// order of its sums cannot depend on the entry point.
 // HBM traffic: MODE 1 and the gradient sweep read Binv's lower triangle once (4 n^2 bytes); MODE 0 reads the points only and is
 // bound by the fp64 exponentials.  Sums: a thread's own in a fixed order, then LDS in a fixed order, then the workspace in a
 // fixed order -- no atomics, the same call twice gives the same bits.
@@ -32,8 +33,7 @@ constexpr int LDC = 16;           // coordinates staged per pass (kmat.hip DC)
 constexpr int LD_THREADS = 256;   // points of a workgroup of lik_derivs_kernel, one per thread
 
 // ---- pointwise derivatives -------------------------------------------------------------------------------------------------
-// (the kernels' bodies are device functions: the single-model kernel runs them as they are, the lock-step kernel moves the
-//  operands to model blockIdx.y first -- one body, so a model's arithmetic does not depend on the entry point)
+// (the kernels' bodies are device functions of ONE model: the kernel moves the operands to model blockIdx.y, then runs the body)
 template <int KIND>
 __device__ __forceinline__ void lik_derivs_body(const double* __restrict__ f, const double* __restrict__ y, int64_t n,
                                                 double* __restrict__ partials, double* __restrict__ d1,
@@ -81,25 +81,18 @@ __device__ __forceinline__ void lik_derivs_body(const double* __restrict__ f, co
   if (tid == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-template <int KIND>
-__global__ __launch_bounds__(LD_THREADS) void lik_derivs_kernel(const double* __restrict__ f, const double* __restrict__ y, int64_t n,
-                                                                double* __restrict__ partials, double* __restrict__ d1,
-                                                                double* __restrict__ w, double* __restrict__ d3) {
-  lik_derivs_body<KIND>(f, y, n, partials, d1, w, d3);
-}
-
 // model blockIdx.y: f + b sf, y + b sy (0: shared), its workgroups' sums at partials + b gridDim.x, outputs [batch, n]
 template <int KIND>
-__global__ __launch_bounds__(LD_THREADS) void lik_derivs_batched_kernel(const double* __restrict__ f, int64_t sf, const double* __restrict__ y,
-                                                                        int64_t sy, int64_t n, double* __restrict__ partials,
-                                                                        double* __restrict__ d1, double* __restrict__ w,
-                                                                        double* __restrict__ d3) {
+__global__ __launch_bounds__(LD_THREADS) void lik_derivs_kernel(const double* __restrict__ f, int64_t sf, const double* __restrict__ y,
+                                                                int64_t sy, int64_t n, double* __restrict__ partials,
+                                                                double* __restrict__ d1, double* __restrict__ w,
+                                                                double* __restrict__ d3) {
   const int64_t b = blockIdx.y;
   lik_derivs_body<KIND>(f + b * sf, y + b * sy, n, partials + b * gridDim.x, d1 ? d1 + b * n : nullptr, w ? w + b * n : nullptr,
                         d3 ? d3 + b * n : nullptr);
 }
 
-// (one workgroup; the lock-step launch: workgroup b adds model b's `count` sums into value[b])
+// (workgroup b adds model b's `count` sums into value[b])
 __global__ __launch_bounds__(256) void lik_derivs_sum_kernel(const double* __restrict__ partials, int64_t count, double* __restrict__ value) {
   partials += (int64_t)blockIdx.x * count;
   value += blockIdx.x;
@@ -137,16 +130,13 @@ struct LapStrides {
   int64_t X, vec, Binv, work;      // vec: every [n] vector (s, v, a, u, d1)
 };
 
+// (what every tile kernel reads; a kernel moves its own vectors and Binv itself, so nothing asks which pointers are null and the
+//  address arithmetic is straight-line.  Model 0 -- every workgroup of a single call -- skips it: its operands are where the
+//  arguments point, and its instruction path is the one a kernel without strides would run)
 __device__ __forceinline__ void lap_model(LapArgs& p, const LapStrides& st, int64_t b) {
   p.X += b * st.X;
   p.variance += b;
   p.ls += b * p.nls;
-  if (p.s) p.s += b * st.vec;
-  if (p.Binv) p.Binv += b * st.Binv;
-  if (p.v) p.v += b * st.vec;
-  if (p.a) p.a += b * st.vec;
-  if (p.u) p.u += b * st.vec;
-  if (p.d1) p.d1 += b * st.vec;
   p.work += b * st.work;
 }
 
@@ -300,13 +290,17 @@ __device__ __forceinline__ void lap_rows_body(const LapArgs& p) {
 }
 
 template <int KIND, int MODE>
-__global__ __launch_bounds__(256) void lap_rows_kernel(LapArgs p) {
-  lap_rows_body<KIND, MODE>(p);
-}
-
-template <int KIND, int MODE>
-__global__ __launch_bounds__(256) void lap_rows_batched_kernel(LapArgs p, LapStrides st) {
-  lap_model(p, st, blockIdx.y);
+__global__ __launch_bounds__(256) void lap_rows_kernel(LapArgs p, LapStrides st) {
+  const int64_t b = blockIdx.y;
+  if (b != 0) {
+    lap_model(p, st, b);
+    if (MODE == 0) {
+      p.v += b * st.vec;
+    } else {
+      p.s += b * st.vec;
+      p.Binv += b * st.Binv;
+    }
+  }
   lap_rows_body<KIND, MODE>(p);
 }
 
@@ -419,13 +413,16 @@ __device__ __forceinline__ void lap_grad_body(const LapArgs& p) {
 }
 
 template <int KIND>
-__global__ __launch_bounds__(256) void lap_grad_kernel(LapArgs p) {
-  lap_grad_body<KIND>(p);
-}
-
-template <int KIND>
-__global__ __launch_bounds__(256) void lap_grad_batched_kernel(LapArgs p, LapStrides st) {
-  lap_model(p, st, blockIdx.y);
+__global__ __launch_bounds__(256) void lap_grad_kernel(LapArgs p, LapStrides st) {
+  const int64_t b = blockIdx.y;
+  if (b != 0) {
+    lap_model(p, st, b);
+    p.s += b * st.vec;
+    p.a += b * st.vec;
+    p.u += b * st.vec;
+    p.d1 += b * st.vec;
+    p.Binv += b * st.Binv;
+  }
   lap_grad_body<KIND>(p);
 }
 
@@ -449,70 +446,95 @@ __global__ __launch_bounds__(256) void lap_grad_reduce_kernel(const double* __re
 
 static int64_t lap_tiles(int64_t n) { return (n + LT - 1) / LT; }
 
-// what every tile entry point checks, in the order of its leading arguments (kind .. nls are arguments 2 .. 8)
-static int lap_check(int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales, int nls) {
-  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;
-  if (!X) return -3;
-  if (n < 0 || n > 0x7fffffff) return -4;
-  if (d <= 0) return -5;
-  if (!variance) return -6;
-  if (!length_scales) return -7;
-  if (nls != 1 && nls != d) return -8;
-  return GPN_OK;
-}
-
-template <int MODE>
-static int lap_rows_launch(hipStream_t s, int kind, const LapArgs& p, const double* divide, double* out) {
-  const int64_t t = p.tiles;
-  if (t * (t + 1) / 2 > 0x7fffffff) return GPN_E_UNSUPPORTED;
-  const dim3 grid((unsigned)(t * (t + 1) / 2));
-  switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL((lap_rows_kernel<GPN_RBF, MODE>), grid, dim3(256), 0, s, p); break;
-    case GPN_MATERN52: hipLaunchKernelGGL((lap_rows_kernel<GPN_MATERN52, MODE>), grid, dim3(256), 0, s, p); break;
-    case GPN_MATERN32: hipLaunchKernelGGL((lap_rows_kernel<GPN_MATERN32, MODE>), grid, dim3(256), 0, s, p); break;
-    case GPN_EXP: hipLaunchKernelGGL((lap_rows_kernel<GPN_EXP, MODE>), grid, dim3(256), 0, s, p); break;
-    default: hipLaunchKernelGGL((lap_rows_kernel<GPN_PERIODIC, MODE>), grid, dim3(256), 0, s, p); break;
-  }
-  GPN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(lap_gather_kernel, dim3((unsigned)((p.n + 255) / 256)), dim3(256), 0, s, p.work, p.tiles, (int64_t)p.n, divide, out,
-                     (int64_t)0, (int64_t)0);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
-}
-
 constexpr int LAP_MAX_BATCH = 65535;      // the model index is a grid's y (z) dimension
 
-// ... and for the lock-step entry points: batch and sX follow kind (arguments 2 .. 10)
-static int lap_check_batched(int kind, int batch, const double* X, int64_t sX, int64_t n, int d, const double* variance,
-                             const double* length_scales, int nls) {
+// what every tile entry point checks, in the order of its leading arguments: kind, X, n .. nls are arguments 2, 3, 4 .. 8 of a
+// single entry point (which passes batch = 1, sX = 0) and, with batch and sX in between, 2, 4, 6 .. 10 of a lock-step one
+static int lap_check(bool lockstep, int kind, int batch, const double* X, int64_t sX, int64_t n, int d, const double* variance,
+                     const double* length_scales, int nls) {
+  const int at_X = lockstep ? 4 : 3, at_n = lockstep ? 6 : 4;
   if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;
   if (batch < 1) return -3;
-  if (!X) return -4;
+  if (!X) return -at_X;
   if (sX < 0) return -5;
-  if (n < 0 || n > 0x7fffffff) return -6;
-  if (d <= 0) return -7;
-  if (!variance) return -8;
-  if (!length_scales) return -9;
-  if (nls != 1 && nls != d) return -10;
+  if (n < 0 || n > 0x7fffffff) return -at_n;
+  if (d <= 0) return -(at_n + 1);
+  if (!variance) return -(at_n + 2);
+  if (!length_scales) return -(at_n + 3);
+  if (nls != 1 && nls != d) return -(at_n + 4);
   return GPN_OK;
 }
 
+// the operands every tile kernel takes (s, Binv, ldb: MODE 1 and the gradient sweep); the caller adds its own vectors
+static LapArgs lap_args(const double* X, int64_t n, int d, const double* variance, const double* length_scales, int nls, const double* s,
+                        const double* Binv, int64_t ldb, double* work) {
+  LapArgs p = {};
+  p.X = X; p.variance = variance; p.ls = length_scales; p.s = s; p.Binv = Binv; p.ldb = ldb; p.work = work;
+  p.n = (int)n; p.d = d; p.nls = nls; p.tiles = (int)lap_tiles(n);
+  return p;
+}
+
+// the pointwise derivatives of `batch` models and, value != nullptr, their sums (blocks: workgroups per model)
+static int lik_derivs_launch(hipStream_t s, int kind, int batch, const double* f, int64_t sf, const double* y, int64_t sy, int64_t n,
+                             int64_t blocks, double* work, double* value, double* d1, double* w, double* d3) {
+  const dim3 grid((unsigned)blocks, (unsigned)batch), block(LD_THREADS);
+  switch (kind) {
+    case GPN_LIK_PROBIT: hipLaunchKernelGGL(lik_derivs_kernel<GPN_LIK_PROBIT>, grid, block, 0, s, f, sf, y, sy, n, work, d1, w, d3); break;
+    case GPN_LIK_LOGIT: hipLaunchKernelGGL(lik_derivs_kernel<GPN_LIK_LOGIT>, grid, block, 0, s, f, sf, y, sy, n, work, d1, w, d3); break;
+    default: hipLaunchKernelGGL(lik_derivs_kernel<GPN_LIK_POISSON>, grid, block, 0, s, f, sf, y, sy, n, work, d1, w, d3); break;
+  }
+  GPN_LAUNCH_CHECK();
+  if (value) {
+    hipLaunchKernelGGL(lik_derivs_sum_kernel, dim3((unsigned)batch), dim3(256), 0, s, work, blocks, value);
+    GPN_LAUNCH_CHECK();
+  }
+  return GPN_OK;
+}
+
+// the tile sweep of `batch` models and the gather of their rows (n > 0)
 template <int MODE>
-static int lap_rows_launch_batched(hipStream_t s, int kind, int batch, const LapArgs& p, const LapStrides& st, const double* divide,
-                                   double* out) {
+static int lap_rows_launch(hipStream_t s, int kind, int batch, const LapArgs& p, const LapStrides& st, const double* divide, double* out) {
   const int64_t t = p.tiles;
   if (t * (t + 1) / 2 > 0x7fffffff || batch > LAP_MAX_BATCH) return GPN_E_UNSUPPORTED;
   const dim3 grid((unsigned)(t * (t + 1) / 2), (unsigned)batch);
   switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL((lap_rows_batched_kernel<GPN_RBF, MODE>), grid, dim3(256), 0, s, p, st); break;
-    case GPN_MATERN52: hipLaunchKernelGGL((lap_rows_batched_kernel<GPN_MATERN52, MODE>), grid, dim3(256), 0, s, p, st); break;
-    case GPN_MATERN32: hipLaunchKernelGGL((lap_rows_batched_kernel<GPN_MATERN32, MODE>), grid, dim3(256), 0, s, p, st); break;
-    case GPN_EXP: hipLaunchKernelGGL((lap_rows_batched_kernel<GPN_EXP, MODE>), grid, dim3(256), 0, s, p, st); break;
-    default: hipLaunchKernelGGL((lap_rows_batched_kernel<GPN_PERIODIC, MODE>), grid, dim3(256), 0, s, p, st); break;
+    case GPN_RBF: hipLaunchKernelGGL((lap_rows_kernel<GPN_RBF, MODE>), grid, dim3(256), 0, s, p, st); break;
+    case GPN_MATERN52: hipLaunchKernelGGL((lap_rows_kernel<GPN_MATERN52, MODE>), grid, dim3(256), 0, s, p, st); break;
+    case GPN_MATERN32: hipLaunchKernelGGL((lap_rows_kernel<GPN_MATERN32, MODE>), grid, dim3(256), 0, s, p, st); break;
+    case GPN_EXP: hipLaunchKernelGGL((lap_rows_kernel<GPN_EXP, MODE>), grid, dim3(256), 0, s, p, st); break;
+    default: hipLaunchKernelGGL((lap_rows_kernel<GPN_PERIODIC, MODE>), grid, dim3(256), 0, s, p, st); break;
   }
   GPN_LAUNCH_CHECK();
   hipLaunchKernelGGL(lap_gather_kernel, dim3((unsigned)((p.n + 255) / 256), (unsigned)batch), dim3(256), 0, s, p.work, p.tiles, (int64_t)p.n,
                      divide, out, st.work, st.vec);
+  GPN_LAUNCH_CHECK();
+  return GPN_OK;
+}
+
+// the gradient sweep of `batch` models (p.a, p.u, p.d1 set; model b's partials st.work after model 0's) and its reduce into
+// out [batch, 1 + nls]
+static int lap_grad_launch(hipStream_t s, int kind, int batch, LapArgs p, const LapStrides& st, double* out) {
+  p.nout = 1 + p.nls;
+  if (p.n == 0) {
+    GPN_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)batch * p.nout * sizeof(double), s));
+    return GPN_OK;
+  }
+  const int64_t t = p.tiles, nblocks = t * (t + 1) / 2;
+  if (nblocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
+  const dim3 grid((unsigned)nblocks, (unsigned)batch);
+  const double n = p.n;
+  int rec = -1;
+  if (profile_on()) rec = profile_begin(s, batch * 8.0 * (0.5 * n * (n + 1.0) + n * p.d), PROF_GRAD);
+  switch (kind) {
+    case GPN_RBF: hipLaunchKernelGGL(lap_grad_kernel<GPN_RBF>, grid, dim3(256), 0, s, p, st); break;
+    case GPN_MATERN52: hipLaunchKernelGGL(lap_grad_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, p, st); break;
+    case GPN_MATERN32: hipLaunchKernelGGL(lap_grad_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, p, st); break;
+    case GPN_EXP: hipLaunchKernelGGL(lap_grad_kernel<GPN_EXP>, grid, dim3(256), 0, s, p, st); break;
+    default: hipLaunchKernelGGL(lap_grad_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, p, st); break;
+  }
+  if (rec >= 0) profile_end(s, rec);
+  GPN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(lap_grad_reduce_kernel, dim3((unsigned)p.nout, (unsigned)batch), dim3(256), 0, s, p.work, nblocks, p.nout, out);
   GPN_LAUNCH_CHECK();
   return GPN_OK;
 }
@@ -537,24 +559,12 @@ extern "C" int gpn_lik_derivs(void* stream, int kind, const double* f, const dou
   const int64_t blocks = (n + LD_THREADS - 1) / LD_THREADS;
   if (blocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
   if (work_bytes < 8 * blocks) return -7;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)blocks), block(LD_THREADS);
-  switch (kind) {
-    case GPN_LIK_PROBIT: hipLaunchKernelGGL(lik_derivs_kernel<GPN_LIK_PROBIT>, grid, block, 0, s, f, y, n, work, d1, w, d3); break;
-    case GPN_LIK_LOGIT: hipLaunchKernelGGL(lik_derivs_kernel<GPN_LIK_LOGIT>, grid, block, 0, s, f, y, n, work, d1, w, d3); break;
-    default: hipLaunchKernelGGL(lik_derivs_kernel<GPN_LIK_POISSON>, grid, block, 0, s, f, y, n, work, d1, w, d3); break;
-  }
-  GPN_LAUNCH_CHECK();
-  if (value) {
-    hipLaunchKernelGGL(lik_derivs_sum_kernel, dim3(1), dim3(256), 0, s, work, blocks, value);
-    GPN_LAUNCH_CHECK();
-  }
-  return GPN_OK;
+  return lik_derivs_launch(static_cast<hipStream_t>(stream), kind, 1, f, 0, y, 0, n, blocks, work, value, d1, w, d3);
 }
 
 extern "C" int gpn_laplace_system(void* stream, int kind, const double* X, int64_t n, int d,
                                   const double* variance, const double* length_scales, int nls, const double* sc, double* A, int64_t lda) {
-  const int rc = lap_check(kind, X, n, d, variance, length_scales, nls);
+  const int rc = lap_check(false, kind, 1, X, 0, n, d, variance, length_scales, nls);
   if (rc != GPN_OK) return rc;
   if (!sc) return -9;
   if (!A) return -10;
@@ -571,22 +581,21 @@ extern "C" int64_t gpn_laplace_rows_work_bytes(int64_t n) {
 
 extern "C" int gpn_laplace_matvec(void* stream, int kind, const double* X, int64_t n, int d,
                                   const double* variance, const double* length_scales, int nls, const double* v, double* work, double* out) {
-  const int rc = lap_check(kind, X, n, d, variance, length_scales, nls);
+  const int rc = lap_check(false, kind, 1, X, 0, n, d, variance, length_scales, nls);
   if (rc != GPN_OK) return rc;
   if (!v) return -9;
   if (!work) return -10;
   if (!out) return -11;
   if (n == 0) return GPN_OK;
-  LapArgs p = {};
-  p.X = X; p.variance = variance; p.ls = length_scales; p.v = v; p.work = work;
-  p.n = (int)n; p.d = d; p.nls = nls; p.tiles = (int)lap_tiles(n);
-  return lap_rows_launch<0>(static_cast<hipStream_t>(stream), kind, p, nullptr, out);
+  LapArgs p = lap_args(X, n, d, variance, length_scales, nls, nullptr, nullptr, 0, work);
+  p.v = v;
+  return lap_rows_launch<0>(static_cast<hipStream_t>(stream), kind, 1, p, LapStrides{}, nullptr, out);
 }
 
 extern "C" int gpn_laplace_diag(void* stream, int kind, const double* X, int64_t n, int d,
                                 const double* variance, const double* length_scales, int nls, const double* sc,
                                 const double* Binv, int64_t ldb, double* work, double* sigma) {
-  const int rc = lap_check(kind, X, n, d, variance, length_scales, nls);
+  const int rc = lap_check(false, kind, 1, X, 0, n, d, variance, length_scales, nls);
   if (rc != GPN_OK) return rc;
   if (!sc) return -9;
   if (!Binv) return -10;
@@ -594,10 +603,8 @@ extern "C" int gpn_laplace_diag(void* stream, int kind, const double* X, int64_t
   if (!work) return -12;
   if (!sigma) return -13;
   if (n == 0) return GPN_OK;
-  LapArgs p = {};
-  p.X = X; p.variance = variance; p.ls = length_scales; p.s = sc; p.Binv = Binv; p.ldb = ldb; p.work = work;
-  p.n = (int)n; p.d = d; p.nls = nls; p.tiles = (int)lap_tiles(n);
-  return lap_rows_launch<1>(static_cast<hipStream_t>(stream), kind, p, sc, sigma);
+  const LapArgs p = lap_args(X, n, d, variance, length_scales, nls, sc, Binv, ldb, work);
+  return lap_rows_launch<1>(static_cast<hipStream_t>(stream), kind, 1, p, LapStrides{}, sc, sigma);
 }
 
 extern "C" int64_t gpn_laplace_grad_work_bytes(int64_t n, int nls) {
@@ -610,7 +617,7 @@ extern "C" int gpn_laplace_grad(void* stream, int kind, const double* X, int64_t
                                 const double* variance, const double* length_scales, int nls, const double* sc,
                                 const double* Binv, int64_t ldb, const double* a, const double* u, const double* d1,
                                 double* work, double* out) {
-  const int rc = lap_check(kind, X, n, d, variance, length_scales, nls);
+  const int rc = lap_check(false, kind, 1, X, 0, n, d, variance, length_scales, nls);
   if (rc != GPN_OK) return rc;
   if (!sc) return -9;
   if (!Binv) return -10;
@@ -620,36 +627,12 @@ extern "C" int gpn_laplace_grad(void* stream, int kind, const double* X, int64_t
   if (!d1) return -14;
   if (!work) return -15;
   if (!out) return -16;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int nout = 1 + nls;
-  if (n == 0) {
-    GPN_HIP_CHECK(hipMemsetAsync(out, 0, nout * sizeof(double), s));
-    return GPN_OK;
-  }
-  LapArgs p = {};
-  p.X = X; p.variance = variance; p.ls = length_scales; p.s = sc; p.Binv = Binv; p.ldb = ldb;
-  p.a = a; p.u = u; p.d1 = d1; p.work = work;
-  p.n = (int)n; p.d = d; p.nls = nls; p.tiles = (int)lap_tiles(n); p.nout = nout;
-  const int64_t t = p.tiles, nblocks = t * (t + 1) / 2;
-  if (nblocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
-  const dim3 grid((unsigned)nblocks);
-  int rec = -1;
-  if (profile_on()) rec = profile_begin(s, 8.0 * (0.5 * n * (n + 1.0) + (double)n * d), PROF_GRAD);
-  switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL(lap_grad_kernel<GPN_RBF>, grid, dim3(256), 0, s, p); break;
-    case GPN_MATERN52: hipLaunchKernelGGL(lap_grad_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, p); break;
-    case GPN_MATERN32: hipLaunchKernelGGL(lap_grad_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, p); break;
-    case GPN_EXP: hipLaunchKernelGGL(lap_grad_kernel<GPN_EXP>, grid, dim3(256), 0, s, p); break;
-    default: hipLaunchKernelGGL(lap_grad_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, p); break;
-  }
-  if (rec >= 0) profile_end(s, rec);
-  GPN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(lap_grad_reduce_kernel, dim3((unsigned)nout), dim3(256), 0, s, work, nblocks, nout, out);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  LapArgs p = lap_args(X, n, d, variance, length_scales, nls, sc, Binv, ldb, work);
+  p.a = a; p.u = u; p.d1 = d1;
+  return lap_grad_launch(static_cast<hipStream_t>(stream), kind, 1, p, LapStrides{}, out);
 }
 
-// ---- the lock-step forms (models/_laplace_lockstep.py): the kernels above with the model index on blockIdx.y ---------------------
+// ---- the lock-step forms (models/_laplace_lockstep.py): the same launches with gridDim.y = batch and the operands' strides --------
 extern "C" int64_t gpn_lik_derivs_batched_work_bytes(int64_t n, int batch) {
   if (batch <= 0) return 0;
   return batch * gpn_lik_derivs_work_bytes(n);
@@ -669,25 +652,13 @@ extern "C" int gpn_lik_derivs_batched(void* stream, int kind, int batch, const d
   const int64_t blocks = (n + LD_THREADS - 1) / LD_THREADS;
   if (blocks > 0x7fffffff || batch > LAP_MAX_BATCH) return GPN_E_UNSUPPORTED;
   if (work_bytes < 8 * blocks * batch) return -10;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const dim3 grid((unsigned)blocks, (unsigned)batch), block(LD_THREADS);
-  switch (kind) {
-    case GPN_LIK_PROBIT: hipLaunchKernelGGL(lik_derivs_batched_kernel<GPN_LIK_PROBIT>, grid, block, 0, s, f, sf, y, sy, n, work, d1, w, d3); break;
-    case GPN_LIK_LOGIT: hipLaunchKernelGGL(lik_derivs_batched_kernel<GPN_LIK_LOGIT>, grid, block, 0, s, f, sf, y, sy, n, work, d1, w, d3); break;
-    default: hipLaunchKernelGGL(lik_derivs_batched_kernel<GPN_LIK_POISSON>, grid, block, 0, s, f, sf, y, sy, n, work, d1, w, d3); break;
-  }
-  GPN_LAUNCH_CHECK();
-  if (value) {
-    hipLaunchKernelGGL(lik_derivs_sum_kernel, dim3((unsigned)batch), dim3(256), 0, s, work, blocks, value);
-    GPN_LAUNCH_CHECK();
-  }
-  return GPN_OK;
+  return lik_derivs_launch(static_cast<hipStream_t>(stream), kind, batch, f, sf, y, sy, n, blocks, work, value, d1, w, d3);
 }
 
 extern "C" int gpn_laplace_system_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                                           const double* variance, const double* length_scales, int nls, const double* sc, int64_t ss,
                                           double* A, int64_t lda, int64_t sA) {
-  const int rc = lap_check_batched(kind, batch, X, sX, n, d, variance, length_scales, nls);
+  const int rc = lap_check(true, kind, batch, X, sX, n, d, variance, length_scales, nls);
   if (rc != GPN_OK) return rc;
   if (!sc) return -11;
   if (ss < 0) return -12;
@@ -708,24 +679,23 @@ extern "C" int64_t gpn_laplace_rows_batched_work_bytes(int64_t n, int batch) {
 extern "C" int gpn_laplace_matvec_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                                           const double* variance, const double* length_scales, int nls, const double* v, int64_t sv,
                                           double* work, double* out) {
-  const int rc = lap_check_batched(kind, batch, X, sX, n, d, variance, length_scales, nls);
+  const int rc = lap_check(true, kind, batch, X, sX, n, d, variance, length_scales, nls);
   if (rc != GPN_OK) return rc;
   if (!v) return -11;
   if (sv < 0) return -12;
   if (!work) return -13;
   if (!out) return -14;
   if (n == 0) return GPN_OK;
-  LapArgs p = {};
-  p.X = X; p.variance = variance; p.ls = length_scales; p.v = v; p.work = work;
-  p.n = (int)n; p.d = d; p.nls = nls; p.tiles = (int)lap_tiles(n);
+  LapArgs p = lap_args(X, n, d, variance, length_scales, nls, nullptr, nullptr, 0, work);
+  p.v = v;
   const LapStrides st = {sX, sv, 0, gpn_laplace_rows_work_bytes(n) / (int64_t)sizeof(double)};
-  return lap_rows_launch_batched<0>(static_cast<hipStream_t>(stream), kind, batch, p, st, nullptr, out);
+  return lap_rows_launch<0>(static_cast<hipStream_t>(stream), kind, batch, p, st, nullptr, out);
 }
 
 extern "C" int gpn_laplace_diag_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                                         const double* variance, const double* length_scales, int nls, const double* sc, int64_t ss,
                                         const double* Binv, int64_t ldb, int64_t sB, double* work, double* sigma) {
-  const int rc = lap_check_batched(kind, batch, X, sX, n, d, variance, length_scales, nls);
+  const int rc = lap_check(true, kind, batch, X, sX, n, d, variance, length_scales, nls);
   if (rc != GPN_OK) return rc;
   if (!sc) return -11;
   if (ss < 0) return -12;
@@ -735,11 +705,9 @@ extern "C" int gpn_laplace_diag_batched(void* stream, int kind, int batch, const
   if (!work) return -16;
   if (!sigma) return -17;
   if (n == 0) return GPN_OK;
-  LapArgs p = {};
-  p.X = X; p.variance = variance; p.ls = length_scales; p.s = sc; p.Binv = Binv; p.ldb = ldb; p.work = work;
-  p.n = (int)n; p.d = d; p.nls = nls; p.tiles = (int)lap_tiles(n);
+  const LapArgs p = lap_args(X, n, d, variance, length_scales, nls, sc, Binv, ldb, work);
   const LapStrides st = {sX, ss, sB, gpn_laplace_rows_work_bytes(n) / (int64_t)sizeof(double)};
-  return lap_rows_launch_batched<1>(static_cast<hipStream_t>(stream), kind, batch, p, st, sc, sigma);
+  return lap_rows_launch<1>(static_cast<hipStream_t>(stream), kind, batch, p, st, sc, sigma);
 }
 
 extern "C" int64_t gpn_laplace_grad_batched_work_bytes(int64_t n, int nls, int batch) {
@@ -751,7 +719,7 @@ extern "C" int gpn_laplace_grad_batched(void* stream, int kind, int batch, const
                                         const double* variance, const double* length_scales, int nls, const double* sc,
                                         const double* Binv, int64_t ldb, int64_t sB, const double* a, const double* u, const double* d1,
                                         int64_t sv, double* work, double* out) {
-  const int rc = lap_check_batched(kind, batch, X, sX, n, d, variance, length_scales, nls);
+  const int rc = lap_check(true, kind, batch, X, sX, n, d, variance, length_scales, nls);
   if (rc != GPN_OK) return rc;
   if (!sc) return -11;
   if (!Binv) return -12;
@@ -764,32 +732,8 @@ extern "C" int gpn_laplace_grad_batched(void* stream, int kind, int batch, const
   if (!work) return -19;
   if (!out) return -20;
   if (batch > LAP_MAX_BATCH) return GPN_E_UNSUPPORTED;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int nout = 1 + nls;
-  if (n == 0) {
-    GPN_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)batch * nout * sizeof(double), s));
-    return GPN_OK;
-  }
-  LapArgs p = {};
-  p.X = X; p.variance = variance; p.ls = length_scales; p.s = sc; p.Binv = Binv; p.ldb = ldb;
-  p.a = a; p.u = u; p.d1 = d1; p.work = work;
-  p.n = (int)n; p.d = d; p.nls = nls; p.tiles = (int)lap_tiles(n); p.nout = nout;
-  const int64_t t = p.tiles, nblocks = t * (t + 1) / 2;
-  if (nblocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
-  const LapStrides st = {sX, sv, sB, nblocks * nout};
-  const dim3 grid((unsigned)nblocks, (unsigned)batch);
-  int rec = -1;
-  if (profile_on()) rec = profile_begin(s, batch * 8.0 * (0.5 * n * (n + 1.0) + (double)n * d), PROF_GRAD);
-  switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL(lap_grad_batched_kernel<GPN_RBF>, grid, dim3(256), 0, s, p, st); break;
-    case GPN_MATERN52: hipLaunchKernelGGL(lap_grad_batched_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, p, st); break;
-    case GPN_MATERN32: hipLaunchKernelGGL(lap_grad_batched_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, p, st); break;
-    case GPN_EXP: hipLaunchKernelGGL(lap_grad_batched_kernel<GPN_EXP>, grid, dim3(256), 0, s, p, st); break;
-    default: hipLaunchKernelGGL(lap_grad_batched_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, p, st); break;
-  }
-  if (rec >= 0) profile_end(s, rec);
-  GPN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(lap_grad_reduce_kernel, dim3((unsigned)nout, (unsigned)batch), dim3(256), 0, s, work, nblocks, nout, out);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  LapArgs p = lap_args(X, n, d, variance, length_scales, nls, sc, Binv, ldb, work);
+  p.a = a; p.u = u; p.d1 = d1;
+  const LapStrides st = {sX, sv, sB, gpn_laplace_grad_work_bytes(n, nls) / (int64_t)sizeof(double)};
+  return lap_grad_launch(static_cast<hipStream_t>(stream), kind, batch, p, st, out);
 }

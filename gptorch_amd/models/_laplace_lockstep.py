@@ -107,7 +107,7 @@ def find_modes(kind, lik_kind, X, Y, M, var, ls, starts, tols, max_iters, fb=Non
         fb = _ops.FactorBatch(B, n, 1, dev)
     fb.generation += 1
     STATS["searches"] += 1
-    work = _ops._rows_work_batched(n, B, dev, None)
+    work = _ops._rows_work(n, dev, None, B)
     modes = [None] * B
 
     def alone(b):

@@ -764,7 +764,8 @@ int gpn_backsub(void* stream, const double* A, int64_t lda, const double* winv, 
                 double* out, int64_t ldo);
 
 /* ---- LaplaceGP in lock step (gptorch_amd/models/_laplace_lockstep.py): the entry points above for `batch` equal-shape models,
- * ONE launch each with the model index on a grid dimension.  Model b reads its points at X + b*sX (sX = 0: shared points, as
+ * ONE launch each with the model index on a grid dimension; a single entry point above is its lock-step twin at batch = 1 with
+ * every stride 0 (the same kernels, one grid row).  Model b reads its points at X + b*sX (sX = 0: shared points, as
  * gpn_kernel_matrix_batched), variance[b], length_scales + b*nls and its vectors at the given strides (in doubles); per model
  * the arithmetic and the order of every sum are the single entry point's, so each model's results are BIT-IDENTICAL to `batch`
  * single calls.  Arguments are validated in order before any launch (-k: the k-th argument, the stream being the first);
