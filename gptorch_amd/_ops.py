@@ -726,6 +726,35 @@ def backsub(f):
     return out
 
 
+EP_STATS = ("sum_log_z", "site_evidence", "max_dtau", "max_dnu", "max_tau", "max_nu")      # gpn_ep_sites' statistics vector
+
+
+def ep_sites(kind, y, m, mu, sigma2, tau, nu, damping, nodes=None, weights=None, moments_only=False, want_moments=True):
+    """gpn_ep_sites: cavity, tilted moments, damped site update and statistics of one EP sweep ->
+    (tau_new [n], nu_new [n], log Z^ [n], mu_hat [n], s2_hat [n], stats [6] as EP_STATS).  moments_only: no update, tau_new / nu_new
+    are None; want_moments=False: the three per-point moments are None.  m: the prior mean at the points or None (zero);
+    nodes / weights: the Gauss-Hermite rule of the logit link (None for probit).  No host synchronisation."""
+    n = y.numel()
+    y, mu, sigma2, tau, nu = (_vec(t, n, what) for t, what in ((y, "y"), (mu, "mu"), (sigma2, "sigma2"), (tau, "tau"), (nu, "nu")))
+    m = None if m is None else _vec(m, n, "m")
+    _req(nodes, weights)
+    dev = y.device
+    lib = _native.lib()
+
+    def new(want, k=n):
+        return torch.empty(k, dtype=torch.float64, device=dev) if want else None
+
+    work = new(True, max(1, int(lib.gpn_ep_sites_work_bytes(n)) // 8))
+    tau_new, nu_new = new(not moments_only), new(not moments_only)
+    lz, mu_hat, s2_hat = new(want_moments), new(want_moments), new(want_moments)
+    stats = new(True, len(EP_STATS))
+    st = lib.gpn_ep_sites(_stream(dev), kind, n, _ptr(y), _ptr(m), _ptr(mu), _ptr(sigma2), _ptr(tau), _ptr(nu), float(damping), _ptr(nodes),
+                          _ptr(weights), 0 if nodes is None else nodes.numel(), int(bool(moments_only)), _ptr(work), work.numel() * 8,
+                          _ptr(tau_new), _ptr(nu_new), _ptr(lz), _ptr(mu_hat), _ptr(s2_hat), _ptr(stats))
+    _native.check(st, "gpn_ep_sites")
+    return tau_new, nu_new, lz, mu_hat, s2_hat, stats
+
+
 # ---- the same in lock step (models/_laplace_lockstep.py): `batch` equal-shape models per launch.  X [n, d] shared or [batch, n, d],
 # variance [batch], length_scales [batch, nls], vectors stacked [batch, n]; every row of every result is bit-identical to the
 # single wrapper called on that model.  No host synchronisation.

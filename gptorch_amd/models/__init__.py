@@ -7,3 +7,4 @@ from .sparse_gpr import SVGP, VFE  # noqa: F401
 from ._fitc import FITC  # noqa: F401
 from .dist_gpr import DistGPR  # noqa: F401
 from .laplace import LaplaceGP  # noqa: F401
+from .ep import EPGP  # noqa: F401

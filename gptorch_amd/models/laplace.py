@@ -40,7 +40,8 @@ batched_factorise run their searches, evidences, gradients and prediction states
 number bit-identical to the model's own evaluation here.
 
 Out of scope: composite kernels, dy > 1, Student-t (not log-concave: W may be negative and B indefinite), ragged (unequal-N)
-lock-step groups, optimize(capture=True) (the search reads the host), DistGPR, expectation propagation.
+lock-step groups, optimize(capture=True) (the search reads the host), DistGPR.  Expectation propagation, the more accurate
+approximation for Bernoulli labels, is models.EPGP (models/ep.py), which runs on these kernels and shares _predict below.
 """
 import sys
 

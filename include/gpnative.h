@@ -763,6 +763,28 @@ int64_t gpn_backsub_work_bytes(int64_t n, int dy);
 int gpn_backsub(void* stream, const double* A, int64_t lda, const double* winv, int64_t n, int dy, double* work,
                 double* out, int64_t ldo);
 
+/* ---- EPGP (gptorch_amd/models/ep.py): the per-point half of one parallel expectation-propagation sweep -------------------
+ * For every point, from the posterior marginal N(mu_i, sigma2_i) and the site parameters (tau_i, nu_i): the cavity
+ * tau_c = 1 / sigma2 - tau, nu_c = mu / sigma2 - nu; the tilted moments log Z^, mu_hat, s2_hat of
+ * p(y_i | f) N(f | nu_c / tau_c, 1 / tau_c) (GPN_LIK_PROBIT: closed form, the left tail through a continued fraction, so
+ * s2_hat > 0 for every cavity with tau_c > 0; GPN_LIK_LOGIT: the H-node Gauss-Hermite rule nodes / weights [H], 2 <= H <= 64; other kinds:
+ * GPN_E_UNSUPPORTED); and, unless moments_only, the damped update (0 < damping <= 1) tau_out = max(tau + damping (1 / s2_hat - tau_c - tau), 0),
+ * nu_out = nu + damping (mu_hat / s2_hat - nu_c - nu) (tau_out / nu_out may be tau / nu themselves).
+ * stats [GPN_EP_NSTATS]: sum log Z^;  sum e_i, the site part of the evidence at the INPUT sites,
+ *   e_i = log Z^ + 1/2 log1p(tau / tau_c) + 1/2 (tau_c c (tau c - 2 w) - w^2) / (tau_c + tau), c = nu_c / tau_c - m_i, w = nu - tau m_i
+ *   (log Z_EP = sum e_i + 1/2 w^T K a - sum log L_ii; no term divides by tau);
+ * max |1 / s2_hat - tau_c - tau| and max |mu_hat / s2_hat - nu_c - nu| (the undamped changes);  max |tau|, max |nu| of the
+ * sites written (moments_only: of the input sites).  A NaN wins a maximum.
+ * m [n]: the prior mean at the points (NULL: zero); lz, mu_hat, s2_hat [n]: each may be NULL; y [n] in {0, 1}.
+ * Arguments are validated before any launch; sums and maxima run in a fixed order without atomics (the same call twice gives
+ * the same bits); nothing is synchronised.  work: work_bytes >= gpn_ep_sites_work_bytes(n). */
+#define GPN_EP_NSTATS 6
+int64_t gpn_ep_sites_work_bytes(int64_t n);
+int gpn_ep_sites(void* stream, int kind, int64_t n, const double* y, const double* m, const double* mu, const double* sigma2,
+                 const double* tau, const double* nu, double damping, const double* nodes, const double* weights, int H,
+                 int moments_only, double* work, int64_t work_bytes, double* tau_out, double* nu_out, double* lz,
+                 double* mu_hat, double* s2_hat, double* stats);
+
 /* ---- LaplaceGP in lock step (gptorch_amd/models/_laplace_lockstep.py): the entry points above for `batch` equal-shape models,
  * ONE launch each with the model index on a grid dimension; a single entry point above is its lock-step twin at batch = 1 with
  * every stride 0 (the same kernels, one grid row).  Model b reads its points at X + b*sX (sX = 0: shared points, as
