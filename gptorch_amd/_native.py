@@ -137,6 +137,11 @@ SIGNATURES = {
     "gpn_ep_sites_work_bytes": (c_int64, [c_int64]),
     "gpn_ep_sites": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p,
                              c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ... in lock step (models/_ep_lockstep.py): `batch` models per launch pair, dampings a device array
+    "gpn_ep_sites_batched_work_bytes": (c_int64, [c_int64, c_int]),
+    "gpn_ep_sites_batched": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p]),
     # ... in lock step (models/_laplace_lockstep.py): `batch` models per launch
     "gpn_lik_derivs_batched_work_bytes": (c_int64, [c_int64, c_int]),
     "gpn_lik_derivs_batched": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64,

@@ -841,6 +841,34 @@ def laplace_grad_batched(kind, X, variance, length_scales, s, Binv, ldb, sB, a, 
     return out
 
 
+def ep_sites_batched(kind, y, m, mu, sigma2, tau, nu, dampings, nodes=None, weights=None, moments_only=False, want_moments=True):
+    """gpn_ep_sites_batched: ep_sites for mu, sigma2, tau, nu [batch, n], y [n] (shared) or [batch, n], m [batch, n] or None and
+    dampings [batch] (a DEVICE tensor: every model its own) -> (tau_new, nu_new, log Z^, mu_hat, s2_hat [batch, n], stats [batch, 6]);
+    an output that is not wanted is None."""
+    batch, n = mu.shape
+    mu, sigma2, tau, nu = (_rows(t, batch, n, what) for t, what in ((mu, "mu"), (sigma2, "sigma2"), (tau, "tau"), (nu, "nu")))
+    y = _vec(y, n, "y") if y.dim() == 1 else _rows(y, batch, n, "y")
+    m = None if m is None else _rows(m, batch, n, "m")
+    dampings = _vec(dampings, batch, "dampings")
+    _req(nodes, weights)
+    dev = mu.device
+    lib = _native.lib()
+
+    def new(want, *shape):
+        return torch.empty(*shape, dtype=torch.float64, device=dev) if want else None
+
+    work = new(True, max(1, int(lib.gpn_ep_sites_batched_work_bytes(n, batch)) // 8))
+    tau_new, nu_new = new(not moments_only, batch, n), new(not moments_only, batch, n)
+    lz, mu_hat, s2_hat = new(want_moments, batch, n), new(want_moments, batch, n), new(want_moments, batch, n)
+    stats = new(True, batch, len(EP_STATS))
+    st = lib.gpn_ep_sites_batched(_stream(dev), kind, batch, n, _ptr(y), 0 if y.dim() == 1 else n, _ptr(m), _ptr(mu), _ptr(sigma2), _ptr(tau),
+                                  _ptr(nu), _ptr(dampings), _ptr(nodes), _ptr(weights), 0 if nodes is None else nodes.numel(),
+                                  int(bool(moments_only)), _ptr(work), work.numel() * 8, _ptr(tau_new), _ptr(nu_new), _ptr(lz), _ptr(mu_hat),
+                                  _ptr(s2_hat), _ptr(stats))
+    _native.check(st, "gpn_ep_sites_batched")
+    return tau_new, nu_new, lz, mu_hat, s2_hat, stats
+
+
 def _addr(t):
     return ctypes.c_void_p(t) if isinstance(t, int) else _ptr(t)
 

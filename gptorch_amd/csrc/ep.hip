@@ -11,6 +11,10 @@
 //                                   c = mu_c - m_i, w = nu - tau m_i: R&W eqs. 3.73-3.74's site terms; nothing divides by tau
 //                       and the workgroup's six statistics (two sums, four maxima) into its slot of the workspace.
 //   ep_stats_kernel     one workgroup adds / maximises the workgroups' slots.
+//   ep_sites_batched_kernel / ep_stats_batched_kernel     the same two bodies (ep_sites_body, ep_stats_body) for `batch` equal-length
+//                       models (models/_ep_lockstep.py), the model on blockIdx.y, its operands at a stride and its own damping from a
+//                       device array: the same points per thread and workgroup, the same trees, the same order over its own slots --
+//                       row b carries the bits of gpn_ep_sites on model b alone.
 // Sums and maxima: a thread's own value, the wavefront's shuffle tree, the four wavefronts as (w0 + w1) + (w2 + w3), then the
 // workgroups' slots in a fixed strided order and the same tree -- no atomics, the same call twice gives the same bits.  A NaN
 // wins every maximum, so that a non-finite input cannot pass the stopping rule.
@@ -73,8 +77,9 @@ struct EpArgs {
   int H, moments_only;
 };
 
+// one workgroup's points of ONE model: the body of both ep_sites_kernel and ep_sites_batched_kernel (p: that model's operands)
 template <int KIND>
-__global__ __launch_bounds__(EP_THREADS) void ep_sites_kernel(EpArgs p) {
+__device__ __forceinline__ void ep_sites_body(const EpArgs& p) {
   __shared__ double rule[2][EP_MAX_H];
   const int tid = threadIdx.x;
   if (KIND == GPN_LIK_LOGIT) {
@@ -115,7 +120,8 @@ __global__ __launch_bounds__(EP_THREADS) void ep_sites_kernel(EpArgs p) {
   ep_block_stats(st, p.partials + blockIdx.x, gridDim.x);
 }
 
-__global__ __launch_bounds__(EP_THREADS) void ep_stats_kernel(const double* __restrict__ partials, int64_t blocks, double* __restrict__ stats) {
+// one model's workgroup slots [6][blocks] -> its six statistics: the body of both stats kernels
+__device__ __forceinline__ void ep_stats_body(const double* __restrict__ partials, int64_t blocks, double* __restrict__ stats) {
   double st[EP_NSTATS];
 #pragma unroll
   for (int k = 0; k < EP_NSTATS; ++k) {
@@ -124,6 +130,37 @@ __global__ __launch_bounds__(EP_THREADS) void ep_stats_kernel(const double* __re
     st[k] = a;
   }
   ep_block_stats(st, stats, 1);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(EP_THREADS) void ep_sites_kernel(EpArgs p) {
+  ep_sites_body<KIND>(p);
+}
+
+__global__ __launch_bounds__(EP_THREADS) void ep_stats_kernel(const double* __restrict__ partials, int64_t blocks, double* __restrict__ stats) {
+  ep_stats_body(partials, blocks, stats);
+}
+
+// ... for `batch` equal-length models, blockIdx.y the model: p holds model 0's operands, every stacked operand of model b lies
+// b * n further on (y: b * sy, sy = 0 shared), its slots b * 6 * gridDim.x, its damping at dampings[b]
+template <int KIND>
+__global__ __launch_bounds__(EP_THREADS) void ep_sites_batched_kernel(EpArgs p, const double* __restrict__ dampings, int64_t sy) {
+  const int64_t b = blockIdx.y, at = b * p.n;
+  p.y += b * sy;
+  if (p.m) p.m += at;
+  p.mu += at, p.sigma2 += at, p.tau += at, p.nu += at;
+  if (!p.moments_only) p.tau_out += at, p.nu_out += at;
+  if (p.lz) p.lz += at;
+  if (p.mu_hat) p.mu_hat += at;
+  if (p.s2_hat) p.s2_hat += at;
+  p.partials += b * EP_NSTATS * (int64_t)gridDim.x;
+  p.damping = dampings[b];
+  ep_sites_body<KIND>(p);
+}
+
+__global__ __launch_bounds__(EP_THREADS) void ep_stats_batched_kernel(const double* __restrict__ partials, int64_t blocks, double* __restrict__ stats) {
+  const int64_t b = blockIdx.y;
+  ep_stats_body(partials + b * EP_NSTATS * blocks, blocks, stats + b * EP_NSTATS);
 }
 
 }  // namespace gpn
@@ -169,6 +206,53 @@ extern "C" int gpn_ep_sites(void* stream, int kind, int64_t n, const double* y, 
   else hipLaunchKernelGGL(ep_sites_kernel<GPN_LIK_LOGIT>, dim3((unsigned)blocks), dim3(EP_THREADS), 0, s, p);
   GPN_LAUNCH_CHECK();
   hipLaunchKernelGGL(ep_stats_kernel, dim3(1), dim3(EP_THREADS), 0, s, work, blocks, stats);
+  GPN_LAUNCH_CHECK();
+  return GPN_OK;
+}
+
+extern "C" int64_t gpn_ep_sites_batched_work_bytes(int64_t n, int batch) {
+  if (batch <= 0) return 0;
+  return batch * gpn_ep_sites_work_bytes(n);
+}
+
+extern "C" int gpn_ep_sites_batched(void* stream, int kind, int batch, int64_t n, const double* y, int64_t sy, const double* m,
+                                    const double* mu, const double* sigma2, const double* tau, const double* nu, const double* dampings,
+                                    const double* nodes, const double* weights, int H, int moments_only, double* work, int64_t work_bytes,
+                                    double* tau_out, double* nu_out, double* lz, double* mu_hat, double* s2_hat, double* stats) {
+  if (kind < GPN_LIK_PROBIT || kind > GPN_LIK_STUDENT_T) return -2;
+  if (kind != GPN_LIK_PROBIT && kind != GPN_LIK_LOGIT) return GPN_E_UNSUPPORTED;
+  if (batch <= 0) return -3;
+  if (batch > 65535) return GPN_E_UNSUPPORTED;      // (a grid dimension)
+  if (n <= 0) return -4;
+  if (!y) return -5;
+  if (sy != 0 && sy != n) return -6;
+  if (!mu) return -8;
+  if (!sigma2) return -9;
+  if (!tau) return -10;
+  if (!nu) return -11;
+  if (!dampings) return -12;                        // (their values live on the device: the caller's to keep in (0, 1])
+  if (kind == GPN_LIK_LOGIT) {
+    if (!nodes) return -13;
+    if (!weights) return -14;
+    if (H < 2 || H > EP_MAX_H) return -15;
+  }
+  if (!work) return -17;
+  const int64_t blocks = (n + EP_THREADS - 1) / EP_THREADS;
+  if (blocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
+  if (work_bytes < gpn_ep_sites_batched_work_bytes(n, batch)) return -18;
+  if (!moments_only && !tau_out) return -19;
+  if (!moments_only && !nu_out) return -20;
+  if (!stats) return -24;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  EpArgs p;
+  p.y = y, p.m = m, p.mu = mu, p.sigma2 = sigma2, p.tau = tau, p.nu = nu, p.nodes = nodes, p.weights = weights;
+  p.tau_out = tau_out, p.nu_out = nu_out, p.lz = lz, p.mu_hat = mu_hat, p.s2_hat = s2_hat, p.partials = work;
+  p.damping = 0.0, p.n = n, p.H = H, p.moments_only = moments_only;
+  const dim3 grid((unsigned)blocks, (unsigned)batch);
+  if (kind == GPN_LIK_PROBIT) hipLaunchKernelGGL(ep_sites_batched_kernel<GPN_LIK_PROBIT>, grid, dim3(EP_THREADS), 0, s, p, dampings, sy);
+  else hipLaunchKernelGGL(ep_sites_batched_kernel<GPN_LIK_LOGIT>, grid, dim3(EP_THREADS), 0, s, p, dampings, sy);
+  GPN_LAUNCH_CHECK();
+  hipLaunchKernelGGL(ep_stats_batched_kernel, dim3(1, (unsigned)batch), dim3(EP_THREADS), 0, s, work, blocks, stats);
   GPN_LAUNCH_CHECK();
   return GPN_OK;
 }

@@ -64,17 +64,18 @@ def _dots(x, y):
     return _ops.dot2d_raw(_ptr(x), n, n, _ptr(y), n, n, 1, n, k, x.device)
 
 
-def _potrf(fb, count):
+def _potrf(fb, count, stats=None):
     fb.info[:count].zero_()
     st = _native.lib().gpn_potrf_lower_batched(_stream(fb.A.device), _ptr(fb.A), fb.n, fb.e, fb.ld, fb.sA, _ptr(fb.winv), fb.sW,
                                                _ptr(fb.info), count)
     _native.check(st, "gpn_potrf_lower_batched")
-    STATS["factorisations"] += count
+    (STATS if stats is None else stats)["factorisations"] += count
 
 
-def _factor_systems(kind, X, var, ls, s, fb, rhs=None):
+def _factor_systems(kind, X, var, ls, s, fb, rhs=None, stats=None):
     """laplace._factor_system for the first s.shape[0] slots of fb: B_b assembled and factorised, rhs [k, n] (None: zeros) forward-
-    substituted on the way; nothing is read back."""
+    substituted on the way; nothing is read back.  stats: the counters that take the factorisations (None: this module's; EP's
+    lock-step search, models/_ep_lockstep.py, hands in its own)."""
     k, n = s.shape
     _ops.laplace_system_batched(kind, X, var, ls, s, fb)
     extra = fb.A.view(fb.batch, fb.rows, fb.ld)[:k, n]
@@ -83,7 +84,7 @@ def _factor_systems(kind, X, var, ls, s, fb, rhs=None):
     else:
         extra[:, n:] = 0.0                       # the corner accumulates -alpha alpha^T (Factor.pack_rhs)
         extra[:, :n] = rhs
-    _potrf(fb, k)
+    _potrf(fb, k, stats)
 
 
 def _sel(t, idx):

@@ -9,7 +9,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from .. import _expr, _ops, mean_functions
+from .. import _expr, _native, _ops, mean_functions
 
 
 class GroupKey(NamedTuple):
@@ -258,7 +258,7 @@ def _laplace_groups(models):
 
 
 def _laplace_group_inputs(ms, differentiable):
-    """(X, Y, variance [B], length scales [B, nls], [m_b = mean_function(X_b)]) of one _laplace_groups group: X and Y shared when
+    """(X, Y, variance [B], length scales [B, nls], [m_b = mean_function(X_b)]) of one _laplace_groups / _ep_groups group: X and Y shared when
     every model holds the same tensors (restarts on one data set), else stacked"""
     m0 = ms[0]
     same_x = all(m.X.data_ptr() == m0.X.data_ptr() for m in ms)
@@ -280,6 +280,42 @@ def _laplace_group_evidence(ms, key, differentiable):
     from . import _laplace_lockstep
     X, Y, var, ls, means = _laplace_group_inputs(ms, differentiable)
     return _laplace_lockstep.BatchedLaplaceEvidence.apply(X, Y, var, ls, key[1], key[2], ms, _batch_holder((key, len(ms))), *means)
+
+
+def _ep_key(m):
+    k = m.kernel
+    link = m._lik_kind
+    # (probit's moments are closed form: its models share a group whatever their likelihood's quadrature setting)
+    H = 0 if link == _native.LIK_PROBIT else int(m.likelihood.num_gauss_hermite_points)
+    return ("ep", k._kind, link, tuple(m.X.shape), int(k.length_scales.numel()), m.X.device, H)
+
+
+def _ep_groups(models):
+    """[(key, indices)] of the EPGP models that can share one lock-step evaluation (_ep_lockstep.BatchedEPEvidence): EPGP's own
+    log_likelihood over points on the GPU, of a size _ep_lockstep.supported() admits, grouped and split into chunks that fit the
+    device's free memory as _laplace_groups does; singletons stay sequential.
+    key = ("ep", kind, likelihood kind, X's shape, number of length scales, device, H), H the number of Gauss-Hermite nodes of the
+    logit link (the group's kernel stages ONE rule) and 0 for probit."""
+    from . import _ep_lockstep
+    from .ep import EPGP
+    groups = {}
+    for i, m in enumerate(models):
+        if not isinstance(m, EPGP) or type(m).log_likelihood is not EPGP.log_likelihood:
+            continue
+        if not (isinstance(m.X, torch.Tensor) and m.X.is_cuda) or not _ep_lockstep.supported(m.X.shape[0]):
+            continue
+        groups.setdefault(_ep_key(m), []).append(i)
+    out = []
+    for key, g in groups.items():
+        out += _chunks(key, g, _capacity(_ep_lockstep.per_model_bytes(key[3][0], key[4]), key[5], held=_held_bytes()))
+    return out
+
+
+def _ep_group_evidence(ms, key, differentiable):
+    """the lock-step evidences [B] of one _ep_groups group (autograd-connected to every model's Params when differentiable)"""
+    from . import _ep_lockstep
+    X, Y, var, ls, means = _laplace_group_inputs(ms, differentiable)
+    return _ep_lockstep.BatchedEPEvidence.apply(X, Y, var, ls, key[1], key[2], ms, _batch_holder((key, len(ms))), *means)
 
 
 def _group_data(ms, differentiable=False, key=None):
@@ -373,6 +409,10 @@ def batched_log_likelihood(models, streams=None):
             ev = _laplace_group_evidence([models[i] for i in g], key, differentiable=False)
             for b, i in enumerate(g):
                 out[i] = ev[b:b + 1]                                         # (LaplaceGP.log_likelihood returns a (1,) tensor)
+        for key, g in _ep_groups(models):
+            ev = _ep_group_evidence([models[i] for i in g], key, differentiable=False)
+            for b, i in enumerate(g):
+                out[i] = ev[b:b + 1]                                         # (EPGP.log_likelihood returns a (1,) tensor)
         for i, m in enumerate(models):
             if out[i] is None:
                 out[i] = m.log_likelihood()
@@ -416,6 +456,22 @@ def batched_factorise(models):
                 mode.factor.A[n, :n] = mode.a
                 m._seed_cached_state(("laplace", key[1]), m.X, mode)
                 seeded += 1
+        for key, g in _ep_groups(models):
+            # EPGP folds: the EP searches in lock step into buffers of their own; every model's prediction cache gets its sites'
+            # state, with a in the factor's extra row as EPGP._mode_for_predict leaves it
+            from . import _ep_lockstep
+            ms = [models[i] for i in g]
+            X, Y, var, ls, means = _laplace_group_inputs(ms, differentiable=False)
+            n = X.shape[-2]
+            sites = _ep_lockstep.find_sites_batched(key[1], key[2], X, Y.reshape(n) if Y.dim() == 2 else Y.reshape(len(ms), n),
+                                                    torch.stack([mu.reshape(n) for mu in means]), var, ls, ms[0]._rule(X.device),
+                                                    [m._start(n) for m in ms], [m.ep_tol for m in ms], [m.max_sweeps for m in ms],
+                                                    [m.damping for m in ms])
+            for m, st in zip(ms, sites):
+                m._remember(st)
+                st.factor.A[n, :n] = st.a
+                m._seed_cached_state(("ep", key[1]), m.X, st)
+                seeded += 1
     return seeded
 
 
@@ -425,14 +481,14 @@ def _has_priors(ms):
 
 def _plan_groups(models):
     """the grouping of batched_loss_and_grad for a list of models: [(lock-step groups), (expression groups), (sparse groups),
-    (LaplaceGP groups)] with each group's "has priors" flag.  Shapes, kernels and priors do not change while a search runs:
+    (LaplaceGP and EPGP groups: their keys begin with "laplace" / "ep")] with each group's "has priors" flag.  Shapes, kernels and priors do not change while a search runs:
     multi_start_optimize plans ONCE and hands the plan to every iteration (the grouping walks every model's parameters and, for composite kernels, rebuilds their
     expression programs: host time that a small-N iteration would spend several times over)."""
     _place_all(models)
     return ([(key, g, _has_priors([models[i] for i in g])) for key, g in _lockstep_groups(models)],
             [(key, g, progs, _has_priors([models[i] for i in g])) for key, g, progs in _expression_groups(models)],
             [(key, g, _has_priors([models[i] for i in g])) for key, g in _vfe_groups(models)],
-            [(key, g, _has_priors([models[i] for i in g])) for key, g in _laplace_groups(models)])
+            [(key, g, _has_priors([models[i] for i in g])) for key, g in _laplace_groups(models) + _ep_groups(models)])
 
 
 def _group_loss_and_grad(value, ms, g, priors, out, keepdim):
@@ -465,7 +521,8 @@ def batched_loss_and_grad(models, _plan=None):
     ladder; parameters with priors add their model's own log_prior() (model.py:158-197); sizes that refine the quadratic
     form refine it per model.  Composite / dense-K kernels and singletons take the sequential path.  Equal-shape LaplaceGP models
     run their mode searches, evidences and closed-form gradients in lock step too (_laplace_groups, models/_laplace_lockstep.py),
-    each model's loss, gradients, warm-start mode and newton_stats bit-identical to its own evaluation."""
+    each model's loss, gradients, warm-start mode and newton_stats bit-identical to its own evaluation; so do equal-shape EPGP
+    models (_ep_groups, models/_ep_lockstep.py): loss, gradients, sites and ep_stats bit-identical per model."""
     plan = _plan if _plan is not None else _plan_groups(models)
     out = [None] * len(models)
     for key, g, priors in plan[0]:
@@ -490,9 +547,10 @@ def batched_loss_and_grad(models, _plan=None):
         ms = [models[i] for i in g]
         _group_loss_and_grad(_vfe_group_bound(ms, key, differentiable=True), ms, g, priors, out, False)
     for key, g, priors in plan[3]:
-        # LaplaceGP restarts / folds of one shape: the Newton searches, evidences and closed-form gradients in lock step
+        # LaplaceGP / EPGP restarts / folds of one shape: the searches, evidences and closed-form gradients in lock step
         ms = [models[i] for i in g]
-        _group_loss_and_grad(_laplace_group_evidence(ms, key, differentiable=True), ms, g, priors, out, True)
+        evidence = _ep_group_evidence if key[0] == "ep" else _laplace_group_evidence
+        _group_loss_and_grad(evidence(ms, key, differentiable=True), ms, g, priors, out, True)
     for i, m in enumerate(models):
         if out[i] is None:
             loss = m.loss()

@@ -39,9 +39,13 @@ Likelihoods: Bernoulli("probit") (closed-form moments, R&W eqs. 3.58 and 3.82) a
 likelihood's own Gauss-Hermite rule of num_gauss_hermite_points nodes: that rule is the model's definition, as it is for
 propagate_log).  Prediction is LaplaceGP._predict over (a, s, the factor) of the converged sites.
 
-Out of scope: EP in lock step (EPGP models handed to multi_start_optimize / batched_log_likelihood / batched_loss_and_grad /
-batched_factorise take the sequential path, each model its own evaluation), optimize(capture=True) (the search reads the host),
-DistGPR, ragged groups, sequential (rank-one) EP, Poisson and other likelihoods, composite kernels, dy > 1.
+Lock step: equal-shape EPGP models handed to multi_start_optimize / batched_log_likelihood / batched_loss_and_grad /
+batched_factorise run their searches, evidences and gradients as one group (models/_ep_lockstep.py, _lockstep._ep_groups), every
+model's numbers bit-identical to its own evaluation; a group's models share the kernel kind, the link, X's shape, ARD or not and,
+for logit, the number of Gauss-Hermite nodes.
+
+Out of scope: optimize(capture=True) (the search reads the host; under multi_start_optimize(capture=True) EPGP models keep their
+own optimize()), DistGPR, ragged groups, sequential (rank-one) EP, Poisson and other likelihoods, composite kernels, dy > 1.
 """
 import torch
 
@@ -115,6 +119,18 @@ def find_sites(kind, lik_kind, X, y, m, var, ls, rule=(None, None), sites0=None,
     return st
 
 
+def _evidence_gradients(kind, X, var, ls, st):
+    """the closed form of the module docstring at one search's sites -> g [1 + nls] = dlog Z_EP/d(variance, length_scales)"""
+    f = st.factor
+    if f.generation != st.generation:
+        # the model's reusable buffer was refactorised by a later forward: rebuild this node's factor privately
+        f = _ops.Factor(f.n, 1, f.device)
+        _factor_system(kind, X, var, ls, st.s, f)
+    Binv = _backward._kinv_lower(f, _backward._upper_inverse(f))
+    zero = torch.zeros_like(st.a)
+    return _ops.laplace_grad(kind, X, var, ls, st.s, Binv, st.a, zero, zero)
+
+
 class EPEvidence(torch.autograd.Function):
     """log Z_EP as ONE autograd node: the EP search in the forward, the closed form of the module docstring in the backward.
     Inputs: the points, the targets [n, 1], m = mean_function(X) [n, 1], the CONSTRAINED variance and length-scales; gradients
@@ -136,16 +152,8 @@ class EPEvidence(torch.autograd.Function):
     def backward(ctx, grad_out):
         X, variance, length_scales = ctx.saved_tensors
         kind, st = ctx.kind, ctx.st
-        var, ls = variance.detach(), length_scales.detach()
-        f = st.factor
-        n = f.n
-        if f.generation != st.generation:
-            # the model's reusable buffer was refactorised by a later forward: rebuild this node's factor privately
-            f = _ops.Factor(n, 1, f.device)
-            _factor_system(kind, X, var, ls, st.s, f)
-        Binv = _backward._kinv_lower(f, _backward._upper_inverse(f))
-        zero = torch.zeros_like(st.a)
-        g = _ops.laplace_grad(kind, X, var, ls, st.s, Binv, st.a, zero, zero)
+        n = st.factor.n
+        g = _evidence_gradients(kind, X, variance.detach(), length_scales.detach(), st)
         go = grad_out.reshape(())
         nls = length_scales.numel()
         return (None, None, (go * st.a).reshape(n, 1) if ctx.needs_input_grad[2] else None,

@@ -827,6 +827,21 @@ int64_t gpn_backsub_batched_work_bytes(int64_t n, int dy, int batch);
 int gpn_backsub_batched(void* stream, int batch, const double* A, int64_t lda, int64_t sA, const double* winv, int64_t sW,
                         int64_t n, int dy, double* work, double* out, int64_t ldo, int64_t so);
 
+/* ---- EPGP in lock step (gptorch_amd/models/_ep_lockstep.py): gpn_ep_sites for `batch` equal-length models in ONE launch pair,
+ * the model on a grid dimension.  mu, sigma2, tau, nu, m (NULL: zero for every model) and every per-point output are stacked
+ * [batch, n] (row b at b*n); y at stride sy (0: shared targets, n: stacked); nodes / weights / H and moments_only are the group's;
+ * dampings [batch] is a DEVICE array (every model keeps its own step; the values are the caller's to keep in (0, 1]);
+ * stats [batch, GPN_EP_NSTATS].  Per model the points of a thread and of a workgroup, the shuffle tree, the wavefronts'
+ * (w0 + w1) + (w2 + w3) and the strided order over the model's own workgroup slots are gpn_ep_sites': row b of every output and of
+ * stats is BIT-IDENTICAL to gpn_ep_sites on model b alone.  No atomics; a NaN wins a maximum.  Arguments are validated in order
+ * before any launch (-k: the k-th argument, the stream being the first); kinds other than probit / logit and batch > 65535 (a grid
+ * dimension): GPN_E_UNSUPPORTED.  work: work_bytes >= gpn_ep_sites_batched_work_bytes(n, batch) = batch * gpn_ep_sites_work_bytes(n). */
+int64_t gpn_ep_sites_batched_work_bytes(int64_t n, int batch);
+int gpn_ep_sites_batched(void* stream, int kind, int batch, int64_t n, const double* y, int64_t sy, const double* m,
+                         const double* mu, const double* sigma2, const double* tau, const double* nu, const double* dampings,
+                         const double* nodes, const double* weights, int H, int moments_only, double* work, int64_t work_bytes,
+                         double* tau_out, double* nu_out, double* lz, double* mu_hat, double* s2_hat, double* stats);
+
 
 /* ---- optional launch profiler (bench.py's roofline legs) ---------------------- */
 /* While enabled, every contraction / assembly / gradient-sweep / leaf launch of this library is bracketed by two HIP events
