@@ -159,6 +159,14 @@ SIGNATURES = {
     "gpn_backsub_batched_work_bytes": (c_int64, [c_int64, c_int, c_int]),
     "gpn_backsub_batched": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p,
                                     c_int64, c_int64]),
+    # leave-one-out cross-validation of the exact GP (csrc/loo.hip)
+    "gpn_loo_terms_work_bytes": (c_int64, [c_int64]),
+    "gpn_loo_terms": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                              c_void_p, c_void_p, c_void_p]),
+    "gpn_loo_scale": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64]),
+    "gpn_loo_grad_work_bytes": (c_int64, [c_int64, c_int]),
+    "gpn_loo_grad": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64,
+                             c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
 }
 LIK_PROBIT, LIK_LOGIT, LIK_POISSON, LIK_STUDENT_T = 0, 1, 2, 3   # include/gpnative.h GPN_LIK_*
 LIK_ROWS_PER_GROUP = 256                                        # GPN_LIK_ROWS_PER_GROUP

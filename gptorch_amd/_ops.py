@@ -1149,4 +1149,158 @@ class DenseLogLik(torch.autograd.Function):
                 (go * G.diagonal().sum()).reshape(1) if ctx.needs_input_grad[2] else None)
 
 
+# ----------------------------------------------------------------------------
+# leave-one-out cross-validation (GPR(objective="loo")): csrc/loo.hip
+# ----------------------------------------------------------------------------
+def _rhs_rows(t, n):
+    """a [dy, n] tensor as row-major right-hand sides: (tensor, leading dimension) -- a copy unless the rows are contiguous (a
+    single row's stride says nothing)"""
+    t = t.detach()
+    if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < n):
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t, max(t.stride(0), n)
+
+
+def loo_terms(Kinv, at, n, dy, qt=None, want_q=True, want_var=True, want_rootd=True, want_value=True):
+    """gpn_loo_terms: from the diagonal of Kinv (row-major) and at = a^T [dy, n] -> (qt [dy, n] = (y_i - mu_i)^T, var [n] = 1 / p_i,
+    rootd [n] = sqrt(d_i), value 0-dim = L_LOO); an output that is not wanted is None.  qt given: a row-major buffer q^T is
+    written into (a right-hand-side buffer for solve_right_lt).  No host synchronisation."""
+    _req(Kinv, at, qt)
+    dev = Kinv.device
+    lib = _native.lib()
+    at, ldat = _rhs_rows(at, n)
+
+    def new(want, *shape):
+        return torch.empty(shape, dtype=torch.float64, device=dev) if want else None
+
+    if qt is None:
+        qt = new(want_q, dy, n)
+    work = new(True, max(1, int(lib.gpn_loo_terms_work_bytes(n)) // 8))
+    var, rootd, value = new(want_var, n), new(want_rootd, n), new(want_value)
+    st = lib.gpn_loo_terms(_stream(dev), n, dy, _ptr(Kinv), Kinv.stride(0), _ptr(at), ldat, _ptr(work), work.numel() * 8,
+                           _ptr(qt), 0 if qt is None else max(qt.stride(0), n), _ptr(var), _ptr(rootd), _ptr(value))
+    _native.check(st, "gpn_loo_terms")
+    return qt, var, rootd, value
+
+
+def loo_scale(Kinv, rootd, n, S):
+    """gpn_loo_scale: S[:n, :n] = P diag(rootd), both triangles, from the lower triangle of Kinv; S: a ZEROED row-major buffer whose
+    padding stays zero."""
+    _req(Kinv, rootd, S)
+    st = _native.lib().gpn_loo_scale(_stream(Kinv.device), n, _ptr(Kinv), Kinv.stride(0), _ptr(_c(rootd)), _ptr(S), S.stride(0))
+    _native.check(st, "gpn_loo_scale")
+    return S
+
+
+def loo_grad(kind, X, variance, length_scales, Q, at, wt):
+    """gpn_loo_grad: [2 + nls] = sum_ij G_ij dK_ij/d(variance, length_scales) (CONSTRAINED values) and tr G, with
+    G = -Q + 1/2 (a w^T + w a^T); Q (row-major, lower triangle read), at = a^T and wt = w^T [dy, n]."""
+    Xc, var, ls, args = _kargs(X, variance, length_scales)
+    _req(Q, at, wt)
+    dy, n = at.shape[0], Xc.shape[0]
+    (at, ldat), (wt, ldwt) = _rhs_rows(at, n), _rhs_rows(wt, n)
+    lib = _native.lib()
+    nls = ls.numel()
+    work = torch.empty(max(1, int(lib.gpn_loo_grad_work_bytes(Xc.shape[0], nls)) // 8), dtype=torch.float64, device=Xc.device)
+    out = torch.empty(2 + nls, dtype=torch.float64, device=Xc.device)
+    st = lib.gpn_loo_grad(_stream(Xc.device), KINDS[kind], *args, _ptr(Q), Q.stride(0), _ptr(at), ldat, _ptr(wt), ldwt, dy,
+                          _ptr(work), work.numel() * 8, _ptr(out))
+    _native.check(st, "gpn_loo_grad")
+    return out
+
+
+class LooState:
+    """what the closed form reads off ONE factorisation f of Kyy with (L^-1 r)^T in its extra rows: Kinv (lower triangle of
+    P = Kyy^-1 = U U^T), at = a^T = (P r)^T, qt = (y_i - mu_i)^T, var = 1 / p_i, rootd = sqrt(d_i), value = L_LOO and, with
+    want_w, wt = w^T = (P q)^T -- q^T L^-T by the factor's right-solve, then one skinny contraction with U, the pair that gives
+    a^T; computed here, while U is alive.  The tensors are this object's own: nothing refers to the factor buffer afterwards."""
+
+    def __init__(self, f, want_w=True):
+        from . import _backward
+        n, dy = f.n, f.e
+        self.n, self.dy, self.rows, self.ld = n, dy, f.rows, f.ld
+        U = _backward._upper_inverse(f)
+        self.Kinv = _backward._kinv_lower(f, U)
+        kpad = round_up(n, 16)
+        self.at = gemm_nt(f.A[n:], U, dy, n, kpad, tri=TRI_B_UPPER)                  # a^T = alpha^T U^T
+        Bt = padded_like_factor(f, dy) if want_w else None
+        qt, self.var, self.rootd, self.value = loo_terms(self.Kinv, self.at, n, dy, qt=Bt)
+        self.wt = None
+        if want_w:
+            f.solve_right_lt(Bt, dy)                                                 # q^T L^-T = q^T U
+            self.wt = gemm_nt(Bt, U, dy, n, kpad, tri=TRI_B_UPPER)                   # w^T = (q^T U) U^T
+            qt = None                                                                # (overwritten by the solve)
+        self.qt = qt
+
+    def scaled_square(self):
+        """S = P diag(sqrt d), both triangles, in a zeroed buffer with the factor's geometry"""
+        return loo_scale(self.Kinv, self.rootd, self.n, zeros(self.rows, self.ld, self.Kinv.device))
+
+
+class GPRLooLik(torch.autograd.Function):
+    """The leave-one-out log predictive density L_LOO = sum_i log p(y_i | y_-i, X, theta) of the exact GP (Rasmussen & Williams
+    5.4.2) as one autograd node with GPRLogLik's inputs; output shape (1,).
+    Forward: the factorisation of GPRLogLik (kernel_factor: the same jitter ladder, the model's reusable factor buffer), U = L^-T,
+    P = U U^T, a^T, the per-point terms (gpn_loo_terms) and w = P q.  The node keeps P, a^T, w^T and sqrt(d) PRIVATELY: its
+    backward never reads the shared factor buffer, so a later forward into that buffer cannot invalidate it.
+    Backward: S = P diag(sqrt d) (gpn_loo_scale), Q = S S^T (one lower contraction), the sweep gpn_loo_grad.
+    Memory: four N x N buffers at the peak of either pass (forward: factor, U, the inversion's workspace, P; backward: factor, P, S, Q)."""
+
+    @staticmethod
+    def forward(ctx, X, R, variance, length_scales, noise, kind, holder):
+        n = R.shape[0]
+        if X.shape[0] != n:
+            raise ValueError("X and Y must have same # data.")
+        f = kernel_factor(kind, X, variance, length_scales, noise, R=R, factor=holder.get("factor"))
+        holder["factor"] = f
+        ctx.kind = kind
+        ctx.state = LooState(f)
+        ctx.save_for_backward(X, variance, length_scales)
+        return ctx.state.value.reshape(1)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        X, variance, length_scales = ctx.saved_tensors
+        s = ctx.state
+        n = s.n
+        S = s.scaled_square()
+        Q = torch.empty(round_up(max(n, 1), 64), s.ld, dtype=torch.float64, device=S.device)
+        gemm_nt(S, S, n, n, round_up(n, 16), C=Q, lower=True)                       # Q = P diag(d) P, lower triangle
+        out = loo_grad(ctx.kind, X, variance, length_scales, Q, s.at, s.wt)
+        nls = length_scales.numel()
+        go = grad_out.reshape(())
+        return (None, -go * s.wt.t() if ctx.needs_input_grad[1] else None, go * out[0:1], go * out[1:1 + nls].reshape(length_scales.shape),
+                go * out[1 + nls:2 + nls], None, None)
+
+
+class DenseLooLik(torch.autograd.Function):
+    """GPRLooLik for a kernel matrix that arrives as a dense tensor (Sum / Product / Linear / White ... kernels), the way DenseLogLik
+    serves the LML: Kyy = K + noise I is factorised natively, P, the terms and S are GPRLooLik's, Q = S S^T is a full contraction,
+    the rank terms 1/2 (a w^T + w a^T) = 1/2 [a w] [w a]^T one skinny one, and dL_LOO/dK = G = -Q + 1/2 (a w^T + w a^T) goes back
+    to autograd as a dense [n, n] gradient for the kernels' own backward sweeps (-w for R, tr G for the noise)."""
+
+    @staticmethod
+    def forward(ctx, K, R, noise):
+        Kyy = K.detach().clone()
+        Kyy.diagonal().add_(noise.detach()[0])
+        ctx.state = LooState(cholesky_factor(Kyy, rhs=R))
+        return ctx.state.value.reshape(1)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        s = ctx.state
+        n, dy = s.n, s.dy
+        S = s.scaled_square()
+        G = gemm_nt(S, S, n, n, round_up(n, 16))                                    # Q, both triangles
+        left = torch.zeros(round_up(n, 16), round_up(2 * dy, 16), dtype=torch.float64, device=S.device)
+        right = torch.zeros_like(left)
+        left[:n, :dy], left[:n, dy:2 * dy] = s.at.t(), s.wt.t()
+        right[:n, :dy], right[:n, dy:2 * dy] = s.wt.t(), s.at.t()
+        gemm_nt(left, right, n, n, round_up(2 * dy, 16), alpha=0.5, beta=-1.0, C=G)  # G = 1/2 (a w^T + w a^T) - Q
+        go = grad_out.reshape(())
+        return (go * G if ctx.needs_input_grad[0] else None,
+                -go * s.wt.t() if ctx.needs_input_grad[1] else None,
+                (go * G.diagonal().sum()).reshape(1) if ctx.needs_input_grad[2] else None)
+
+
 LOG_2PI = math.log(2.0 * math.pi)

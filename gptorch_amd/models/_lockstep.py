@@ -142,7 +142,7 @@ def _lockstep_groups(models, for_grad=False):
         k = m._stationary()
         if k is None or not m.X.is_cuda or m.X.shape[0] == 0:
             continue
-        if for_grad and _has_priors([m]):
+        if for_grad and (_has_priors([m]) or m.objective != "lml"):      # (another objective: loss() is formed by the model itself)
             continue
         groups.setdefault(_group_key(m), []).append(i)
     out, pool = [], {}
@@ -485,6 +485,7 @@ def _plan_groups(models):
     multi_start_optimize plans ONCE and hands the plan to every iteration (the grouping walks every model's parameters and, for composite kernels, rebuilds their
     expression programs: host time that a small-N iteration would spend several times over)."""
     _place_all(models)
+    models = [m if getattr(m, "objective", "lml") == "lml" else None for m in models]   # another objective: that model's own loss(), sequentially
     return ([(key, g, _has_priors([models[i] for i in g])) for key, g in _lockstep_groups(models)],
             [(key, g, progs, _has_priors([models[i] for i in g])) for key, g, progs in _expression_groups(models)],
             [(key, g, _has_priors([models[i] for i in g])) for key, g in _vfe_groups(models)],

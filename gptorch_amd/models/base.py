@@ -195,6 +195,8 @@ class GPModel(Model):
             return False
         if type(self).log_likelihood.__qualname__ != "GPR.log_likelihood":      # VFE / DistGPR / user subclasses: their own path
             return False
+        if getattr(self, "objective", "lml") != "lml":                          # GPR(objective="loo"): the ordinary loop
+            return False
         return True
 
     def _captured_loop(self, trainable, make_optimizer, step, dev_losses, max_iter):

@@ -78,8 +78,11 @@ class _DistExprLogLik(torch.autograd.Function):
 
 
 class DistGPR(GPR):
-    def __init__(self, x, y, kernel, mean_function=None, likelihood=None, name="dist_gpr", tile=2048, grid=None, tile_ops=None, schedule=None):
-        super().__init__(x, y, kernel, mean_function=mean_function, likelihood=likelihood, name=name)
+    def __init__(self, x, y, kernel, mean_function=None, likelihood=None, name="dist_gpr", tile=2048, grid=None, tile_ops=None, schedule=None,
+                 objective="lml"):
+        if objective == "loo":
+            raise NotImplementedError("DistGPR fits the log marginal likelihood only: the leave-one-out objective needs the explicit inverse on one GPU")
+        super().__init__(x, y, kernel, mean_function=mean_function, likelihood=likelihood, name=name, objective=objective)
         self._prog = None
         if not (isinstance(kernel, kernels.Stationary) and kernel._kind is not None):
             from .. import _native

@@ -18,8 +18,13 @@ BLOCKED_AFTER_CALLS = 1      # ... and before the 1024 x 1024 diagonal blocks ar
 
 
 class GPR(GPModel):
-    def __init__(self, x, y, kernel, mean_function=None, likelihood=None, name="gpr"):
+    def __init__(self, x, y, kernel, mean_function=None, likelihood=None, name="gpr", objective="lml"):
+        """objective: what loss() / optimize() fit -- "lml", the log marginal likelihood (the reference's only objective), or "loo",
+        the leave-one-out log predictive density (loo_log_predictive).  log_likelihood() is the LML either way."""
         super().__init__(x, y, kernel, likelihood, mean_function, name)
+        if objective not in ("lml", "loo"):
+            raise ValueError("objective must be 'lml' or 'loo'; got %r" % (objective,))
+        self.objective = objective
         self._holder = {}        # reusable factor buffer for the training loop
         self._predict_cache = None
         self._predict_calls = 0
@@ -56,6 +61,46 @@ class GPR(GPModel):
             return _ops.DenseLogLik.apply(self.kernel.K(x), resid, self.likelihood.variance.transform())
         return _ops.GPRLogLik.apply(x, resid, k.variance.transform(), k.length_scales.transform(),
                                     self.likelihood.variance.transform(), k._kind, self._holder)
+
+    def loo_log_predictive(self, x=None, y=None):
+        """sum_i log p(y_i | X, y_-i, theta), the leave-one-out log predictive density in closed form from ONE factorisation
+        (Rasmussen & Williams 5.4.2, eqs. 5.10-5.13); differentiable, shape (1,).  Kernels without a native kind (composites
+        included) hand their dense K(x) to the same native steps."""
+        x = x if x is not None else self.X
+        y = y if y is not None else self.Y
+        if not x.shape[0] == y.shape[0]:
+            raise ValueError("X and Y must have same # data.")
+        k = self._stationary()
+        resid = y - self.mean_function(x)
+        if k is None:
+            return _ops.DenseLooLik.apply(self.kernel.K(x), resid, self.likelihood.variance.transform())
+        return _ops.GPRLooLik.apply(x, resid, k.variance.transform(), k.length_scales.transform(),
+                                    self.likelihood.variance.transform(), k._kind, self._holder)
+
+    def loo_predict(self, x=None, y=None):
+        """(mean [n, dy], var [n, dy]) of every OBSERVATION y_i given all the others (noise included: the predictive that
+        loo_log_predictive scores), from one factorisation; no gradients."""
+        self._auto_place()
+        x = x if x is not None else self.X
+        y = y if y is not None else self.Y
+        if not x.shape[0] == y.shape[0]:
+            raise ValueError("X and Y must have same # data.")
+        with torch.no_grad():
+            k = self._stationary()
+            resid = y - self.mean_function(x)
+            noise = self.likelihood.variance.transform()
+            if k is None:
+                f = _ops.cholesky_factor(self._compute_kyy(x), rhs=resid)
+            else:
+                f = _ops.kernel_factor(k._kind, x, k.variance.transform(), k.length_scales.transform(), noise, R=resid)
+            s = _ops.LooState(f, want_w=False)
+            return y - s.qt.t(), s.var[:, None].expand(y.shape[0], y.shape[1]).clone()
+
+    def _loss(self, *args, **kwargs):
+        if self.objective == "lml":
+            return super()._loss(*args, **kwargs)
+        self._auto_place()
+        return -(self.loo_log_predictive(*args, **kwargs) + self.log_prior())
 
     def _compute_kyy(self, x=None):
         """K(x) + sigma_n^2 I as a dense tensor (gpr.py:69-86); API parity only --

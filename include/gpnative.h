@@ -842,6 +842,33 @@ int gpn_ep_sites_batched(void* stream, int kind, int batch, int64_t n, const dou
                          const double* nodes, const double* weights, int H, int moments_only, double* work, int64_t work_bytes,
                          double* tau_out, double* nu_out, double* lz, double* mu_hat, double* s2_hat, double* stats);
 
+/* ---- leave-one-out cross-validation of the exact GP (GPR(objective="loo"); Rasmussen & Williams 5.4.2) --------------------
+ * With P = Kyy^-1 (its lower triangle, as gpn_trtri_upper + the U U^T contraction leave it), a = P r for the residual r [n, dy]
+ * and p_i = P_ii: the held-out residual y_i - mu_i = q_i = a_i / p_i, the held-out variance of the observation 1 / p_i,
+ *   L_LOO = sum_i [1/2 dy log p_i - 1/2 sum_c a_ic q_ic] - 1/2 n dy log 2 pi,
+ * and with d_i = dy / (2 p_i) + sum_c a_ic^2 / (2 p_i^2), w = P q, Q = P diag(d) P:
+ *   dL_LOO/dtheta = sum_ij G_ij dKyy_ij/dtheta,  G = -Q + 1/2 (a w^T + w a^T),  dL_LOO/dnoise = tr G,  dL_LOO/dr = -w.
+ * Every entry validates its arguments before any launch (-k: the k-th argument, the stream being the first), adds up in a fixed
+ * order without atomics (the same call twice gives the same bits) and synchronises nothing. */
+/* Per point, from the DIAGONAL of Kinv (ldk) and at = a^T [dy, n] (ldat), dy >= 1: qt = q^T [dy, n] (ldqt), var [n] = 1 / p,
+ * rootd [n] = sqrt(d), value[0] = L_LOO; each output may be NULL and the others keep their bits.  A p_i that is not a positive
+ * finite number makes that point's outputs and the value NaN (nothing is clamped).
+ * work: work_bytes >= gpn_loo_terms_work_bytes(n). */
+int64_t gpn_loo_terms_work_bytes(int64_t n);
+int gpn_loo_terms(void* stream, int64_t n, int dy, const double* Kinv, int64_t ldk, const double* at, int64_t ldat,
+                  double* work, int64_t work_bytes, double* qt, int64_t ldqt, double* var, double* rootd, double* value);
+/* S_ij = P_ij rootd_j for all i, j < n -- BOTH triangles -- from the lower triangle of Kinv (ldk), into S (lds): one workgroup
+ * per lower 64 x 64 tile writes the tile and its mirror.  Nothing outside [n, n] is written: in a zeroed buffer with the geometry of
+ * a factor buffer the padding that gpn_gemm_nt reads stays zero, and Q = P diag(d) P (lower) = gpn_gemm_nt(S, S, lower = 1). */
+int gpn_loo_scale(void* stream, int64_t n, const double* Kinv, int64_t ldk, const double* rootd, double* S, int64_t lds);
+/* out[0] = sum_ij G_ij dK_ij/d variance, out[1 .. nls] = sum_ij G_ij dK_ij/d length_scales (CONSTRAINED values),
+ * out[1 + nls] = tr G, with G_ij = -Q_ij + 1/2 sum_c (a_ic w_jc + w_ic a_jc) never materialised: the sweep of gpn_lml_grad over the
+ * lower tiles (K and dK re-computed from the points; any d; every native kind), Q read from its lower triangle (ldq),
+ * at = a^T and wt = w^T [dy, n] (ldat, ldwt).  work: work_bytes >= gpn_loo_grad_work_bytes(n, nls). */
+int64_t gpn_loo_grad_work_bytes(int64_t n, int nls);
+int gpn_loo_grad(void* stream, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
+                 int nls, const double* Q, int64_t ldq, const double* at, int64_t ldat, const double* wt, int64_t ldwt, int dy,
+                 double* work, int64_t work_bytes, double* out);
 
 /* ---- optional launch profiler (bench.py's roofline legs) ---------------------- */
 /* While enabled, every contraction / assembly / gradient-sweep / leaf launch of this library is bracketed by two HIP events
