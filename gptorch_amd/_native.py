@@ -167,6 +167,14 @@ SIGNATURES = {
     "gpn_loo_grad_work_bytes": (c_int64, [c_int64, c_int]),
     "gpn_loo_grad": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_int64,
                              c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    # ... in lock step: the same kernels, the model on the grid's y dimension
+    "gpn_loo_terms_batched_work_bytes": (c_int64, [c_int64, c_int]),
+    "gpn_loo_terms_batched": (c_int, [c_void_p, c_int, c_int64, c_int, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p,
+                                      c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "gpn_loo_scale_batched": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int64]),
+    "gpn_loo_grad_batched_work_bytes": (c_int64, [c_int64, c_int, c_int]),
+    "gpn_loo_grad_batched": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64,
+                                     c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
 }
 LIK_PROBIT, LIK_LOGIT, LIK_POISSON, LIK_STUDENT_T = 0, 1, 2, 3   # include/gpnative.h GPN_LIK_*
 LIK_ROWS_PER_GROUP = 256                                        # GPN_LIK_ROWS_PER_GROUP

@@ -1273,6 +1273,190 @@ class GPRLooLik(torch.autograd.Function):
                 go * out[1 + nls:2 + nls], None, None)
 
 
+# ---- the same in lock step: `batch` equal-shape models per launch (gpn_loo_*_batched: the single kernels with the model on the grid's
+# y dimension).  Operands are device ADDRESSES (or tensors) with a leading dimension and a model stride in doubles, because they live
+# inside gpn_lml_kinv_batched's workspace; every row of every result is bit-identical to the single wrapper called on that model.
+def loo_terms_batched(batch, n, dy, Kinv, ldk, sK, at, ldat, sAt, device, qt=None, ldqt=0, sQt=0, want_var=True, want_rootd=True,
+                      want_value=True):
+    """gpn_loo_terms_batched -> (var [batch, n], rootd [batch, n], value [batch]); qt (address / tensor, ldqt, sQt): q^T of model b is
+    written at qt + b sQt, None: not wanted."""
+    lib = _native.lib()
+
+    def new(want, *shape):
+        return torch.empty(shape, dtype=torch.float64, device=device) if want else None
+
+    work = new(True, max(1, int(lib.gpn_loo_terms_batched_work_bytes(n, batch)) // 8))
+    var, rootd, value = new(want_var, batch, n), new(want_rootd, batch, n), new(want_value, batch)
+    st = lib.gpn_loo_terms_batched(_stream(device), batch, n, dy, _addr(Kinv), ldk, sK, _addr(at), ldat, sAt, _ptr(work), work.numel() * 8,
+                                   None if qt is None else _addr(qt), ldqt, sQt, _ptr(var), _ptr(rootd), _ptr(value))
+    _native.check(st, "gpn_loo_terms_batched")
+    return var, rootd, value
+
+
+def loo_scale_batched(batch, n, Kinv, ldk, sK, rootd, S, lds, sS):
+    """gpn_loo_scale_batched: S_b[:n, :n] = P_b diag(rootd[b]), both triangles; rootd [batch, n]; Kinv, S: addresses / tensors."""
+    _req(rootd)
+    st = _native.lib().gpn_loo_scale_batched(_stream(rootd.device), batch, n, _addr(Kinv), ldk, sK, _ptr(_c(rootd)), _addr(S), lds, sS)
+    _native.check(st, "gpn_loo_scale_batched")
+
+
+def loo_grad_batched(kind, X, variance, length_scales, Q, ldq, sQ, at, ldat, sAt, wt, ldwt, sWt, dy, work=None):
+    """gpn_loo_grad_batched: [batch, 2 + nls], row b = loo_grad of model b (Q, at, wt: addresses / tensors with their leading dimension
+    and model stride)."""
+    Xc, var, ls, batch, n, args = _kargs_batched(X, variance, length_scales)
+    lib = _native.lib()
+    nls = ls.shape[1]
+    need = max(1, int(lib.gpn_loo_grad_batched_work_bytes(n, nls, batch)) // 8)
+    if work is None or work.numel() < need:
+        work = torch.empty(need, dtype=torch.float64, device=Xc.device)
+    out = torch.empty(batch, 2 + nls, dtype=torch.float64, device=Xc.device)
+    st = lib.gpn_loo_grad_batched(_stream(Xc.device), KINDS[kind], *args, _addr(Q), ldq, sQ, _addr(at), ldat, sAt, _addr(wt), ldwt, sWt, dy,
+                                  _ptr(work), work.numel() * 8, _ptr(out))
+    _native.check(st, "gpn_loo_grad_batched")
+    return out
+
+
+class LooGroupState:
+    """LooState for the `batch` models of one lock-step group, every launch once over all of them: the factors of
+    lml_forward_batched (holder["fb"]), gpn_lml_kinv_batched's workspace `wk` (per model: U at offset 0 -- later S --, P, a^T), q^T
+    into right-hand-side buffers padded like the factor, the right-solve and the skinny contraction with U for w^T.  rootd, wt and
+    value are this object's own tensors; P and a^T stay in the holder's workspace, valid while holder["loo_generation"] == generation.
+    No host synchronisation (the caller reads fb.info)."""
+
+    def __init__(self, kind, X, R, variance, length_scales, noise, holder):
+        lib = _native.lib()
+        batch, n, dy = int(variance.numel()), R.shape[-2], R.shape[-1]
+        dev = X.device
+        fb, _terms = lml_forward_batched(kind, X, R, variance, length_scales, noise, fb=holder.get("fb"), refine=False)
+        holder["fb"] = fb
+        holder["loo_generation"] = self.generation = holder.get("loo_generation", 0) + 1
+        self.holder, self.fb, self.batch, self.n, self.dy = holder, fb, batch, n, dy
+        lay = (ctypes.c_int64 * 4)()
+        _native.check(lib.gpn_lml_kinv_layout(n, dy, lay), "gpn_lml_kinv_layout")
+        self.ld, self.koff, self.aoff, self.stride = (int(v) for v in lay)
+        need = max(1, int(lib.gpn_lml_kinv_batched_work_bytes(n, dy, batch)) // 8)
+        if fb._backward_work is None or fb._backward_work.numel() < need:
+            fb._backward_work = torch.empty(need, dtype=torch.float64, device=dev)
+            holder["loo_dirty"] = False
+        self.wk = wk = fb._backward_work
+        s = _stream(dev)
+        if holder.get("loo_dirty") and n > 256 and n % LEAF == 0:
+            # an earlier backward left S where U goes: the inversion gets the zeroed slot it is documented to start from (at the other
+            # sizes gpn_lml_kinv_batched clears the slot itself)
+            urows = int(lib.gpn_factor_rows(n, 0))
+            for b in range(batch):
+                _native.check(lib.gpn_fill_zero(s, wk.data_ptr() + 8 * b * self.stride, 8 * urows * self.ld), "gpn_fill_zero")
+            holder["loo_dirty"] = False
+        _native.check(lib.gpn_lml_kinv_batched(s, batch, n, _ptr(fb.A), fb.ld, fb.sA, _ptr(fb.winv), fb.sW, dy, _ptr(wk)), "gpn_lml_kinv_batched")
+        base = wk.data_ptr()
+        self.kinv_addr, self.at_addr = base + 8 * self.koff, base + 8 * self.aoff
+        brows = round_up(max(dy, 1), LEAF)
+        Bt = holder.get("loo_rhs")
+        if Bt is None or tuple(Bt.shape) != (batch * brows, fb.ld) or Bt.device != dev:
+            Bt = holder["loo_rhs"] = torch.empty(batch * brows, fb.ld, dtype=torch.float64, device=dev)
+        _native.check(lib.gpn_fill_zero(s, _ptr(Bt), Bt.numel() * 8), "gpn_fill_zero")
+        self.var, self.rootd, self.value = loo_terms_batched(batch, n, dy, self.kinv_addr, self.ld, self.stride, self.at_addr, self.ld,
+                                                             self.stride, dev, qt=Bt, ldqt=fb.ld, sQt=brows * fb.ld)
+        self.wt = torch.empty(batch, dy, n, dtype=torch.float64, device=dev)
+        if n:
+            st = lib.gpn_trsm_right_lt_batched(s, _ptr(fb.A), n, fb.ld, fb.sA, _ptr(fb.winv), fb.sW, _ptr(Bt), dy, fb.ld, brows * fb.ld, batch)
+            _native.check(st, "gpn_trsm_right_lt_batched")                            # q^T L^-T = q^T U
+            st = lib.gpn_gemm_nt_batched(s, dy, n, round_up(n, 16), 1.0, _ptr(Bt), fb.ld, brows * fb.ld, _addr(base), self.ld, self.stride,
+                                         0.0, _ptr(self.wt), n, dy * n, 0, TRI_B_UPPER, batch)
+            _native.check(st, "gpn_gemm_nt_batched")                                  # w^T = (q^T U) U^T
+
+    def valid(self):
+        return self.holder.get("loo_generation") == self.generation and self.holder.get("fb") is self.fb and self.fb._backward_work is self.wk
+
+    def grads(self, kind, X, variance, length_scales):
+        """[batch, 2 + nls]: gpn_loo_scale_batched (S into U's slot: U is not read again), ONE lower contraction Q = S S^T over the
+        group, gpn_loo_grad_batched"""
+        lib = _native.lib()
+        batch, n, dy, holder = self.batch, self.n, self.dy, self.holder
+        dev = self.wk.device
+        base = self.wk.data_ptr()
+        qrows = round_up(max(n, 1), 64)
+        Q = holder.get("loo_q")
+        if Q is None or tuple(Q.shape) != (batch, qrows, self.ld) or Q.device != dev:
+            Q = holder["loo_q"] = torch.empty(batch, qrows, self.ld, dtype=torch.float64, device=dev)
+        holder["loo_dirty"] = True
+        loo_scale_batched(batch, n, self.kinv_addr, self.ld, self.stride, self.rootd, base, self.ld, self.stride)
+        if n:
+            st = lib.gpn_gemm_nt_batched(_stream(dev), n, n, round_up(n, 16), 1.0, _addr(base), self.ld, self.stride, _addr(base), self.ld, self.stride,
+                                         0.0, _ptr(Q), self.ld, qrows * self.ld, 1, 0, batch)
+            _native.check(st, "gpn_gemm_nt_batched")
+        nls = length_scales.reshape(batch, -1).shape[1]
+        need = max(1, int(lib.gpn_loo_grad_batched_work_bytes(n, nls, batch)) // 8)
+        work = holder.get("loo_sweep")
+        if work is None or work.numel() < need or work.device != dev:
+            work = holder["loo_sweep"] = torch.empty(need, dtype=torch.float64, device=dev)
+        return loo_grad_batched(kind, X, variance, length_scales, Q, self.ld, qrows * self.ld, self.at_addr, self.ld, self.stride,
+                                self.wt, n, dy * n, dy, work=work)
+
+
+LOO_HOLDER_BUFFERS = ("loo_rhs", "loo_q", "loo_sweep")     # what a LOO group's holder keeps beside its FactorBatch (models/_lockstep.py)
+
+
+class BatchedGPRLooLik(torch.autograd.Function):
+    """GPRLooLik for `batch` independent models of one shape in LOCK STEP (restarts and kernel choices of a leave-one-out fit): the
+    inputs of BatchedGPRLogLik without n_of -> L_LOO [batch].  Forward: LooGroupState (gpn_lml_forward_batched, gpn_lml_kinv_batched,
+    gpn_loo_terms_batched, gpn_trsm_right_lt_batched + gpn_gemm_nt_batched); ONE read of `info` for the group; a model whose
+    factorisation reports info != 0 is replayed ALONE through kernel_factor's jitter ladder + LooState, and its backward runs on that
+    private state.  Backward: gpn_loo_scale_batched, one gpn_gemm_nt_batched (lower), gpn_loo_grad_batched, dL/dR = -w.  The state
+    lives in the group's cached buffers under a generation stamp: a backward that finds it moved (a later forward reused the buffers)
+    rebuilds its state privately.  Values and gradients are bit-identical, model by model, to GPRLooLik.
+    Memory per model: the factor, U (later S), P and Q -- four padded N x N matrices (models/_loo_lockstep.per_model_bytes)."""
+
+    @staticmethod
+    def forward(ctx, X, R, variance, length_scales, noise, kind, holder):
+        batch = int(variance.numel())
+        if X.shape[-2] != R.shape[-2]:
+            raise ValueError("X and Y must have same # data.")
+        state = LooGroupState(kind, X, R, variance, length_scales, noise, holder)
+        out = state.value.clone()
+        info = state.fb.info.cpu()                   # ONE read-back for the group
+        replayed = {}
+        for b in (torch.nonzero(info).reshape(-1).tolist() if bool(info.any()) else ()):
+            f = kernel_factor(kind, X if X.dim() == 2 else X[b], variance.reshape(batch)[b:b + 1], length_scales.reshape(batch, -1)[b],
+                              noise.reshape(batch)[b:b + 1], R=R if R.dim() == 2 else R[b])
+            replayed[b] = (LooState(f), f.jitter_rung)
+            out[b] = replayed[b][0].value
+        holder["loo_replayed"] = {b: rung for b, (_s, rung) in replayed.items()}
+        ctx.kind, ctx.state, ctx.replayed = kind, state, replayed
+        ctx.save_for_backward(X, R, variance, length_scales, noise)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        X, R, variance, length_scales, noise = ctx.saved_tensors
+        batch = int(variance.numel())
+        state = ctx.state
+        if not state.valid():
+            # the group's buffers were reused by a later forward: this node's P and a^T are gone, rebuild them in buffers of its own
+            state = LooGroupState(ctx.kind, X, R, variance, length_scales, noise, {})
+        n, dy = state.n, state.dy
+        grads = state.grads(ctx.kind, X, variance, length_scales)
+        nls = grads.shape[1] - 2
+        need_r = ctx.needs_input_grad[1]
+        g_R = (-state.wt).transpose(1, 2) if need_r else None                        # dL/dR = -w, [batch, n, dy] (a tensor of its own)
+        for b, (s, _rung) in ctx.replayed.items():
+            S = s.scaled_square()
+            Q = torch.empty(round_up(max(n, 1), 64), s.ld, dtype=torch.float64, device=S.device)
+            gemm_nt(S, S, n, n, round_up(n, 16), C=Q, lower=True)
+            grads[b] = loo_grad(ctx.kind, X if X.dim() == 2 else X[b], variance.reshape(batch)[b:b + 1], length_scales.reshape(batch, -1)[b],
+                                Q, s.at, s.wt)
+            if need_r:
+                g_R[b] = -s.wt.t()
+        go = grad_out.reshape(batch)
+        g_resid = None
+        if need_r:
+            g_resid = go[:, None, None] * g_R
+            if R.dim() == 2:
+                g_resid = g_resid.sum(0)
+        return (None, g_resid, (go * grads[:, 0]).reshape(variance.shape), (go[:, None] * grads[:, 1:1 + nls]).reshape(length_scales.shape),
+                (go * grads[:, 1 + nls]).reshape(noise.shape), None, None)
+
+
 class DenseLooLik(torch.autograd.Function):
     """GPRLooLik for a kernel matrix that arrives as a dense tensor (Sum / Product / Linear / White ... kernels), the way DenseLogLik
     serves the LML: Kyy = K + noise I is factorised natively, P, the terms and S are GPRLooLik's, Q = S S^T is a full contraction,

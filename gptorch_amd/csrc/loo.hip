@@ -19,6 +19,10 @@
 // HBM traffic: loo_scale reads 4 n^2 bytes and writes 8 n^2; loo_grad reads 4 n^2 and is otherwise bound by the fp64
 // exponentials.  Sums: a thread's own in a fixed order, then the wavefront's shuffle tree / LDS in a fixed order, then the
 // workspace in a fixed order -- no atomics, the same call twice gives the same bits.  Nothing synchronises.
+// One kernel per operation: every kernel takes `batch` equal-shape models in one launch, the model index on blockIdx.y and model
+// b's operands at pointer + b * stride (strides in doubles; sX = 0: shared points).  The lock-step entry points (gpn_loo_*_batched;
+// _ops.BatchedGPRLooLik) launch gridDim.y = batch; a single entry point is its lock-step twin at batch = 1, so a model's
+// arithmetic and the order of its sums cannot depend on the entry point.
 #include "kernel_fn.h"
 #include "rowkernels.h"
 
@@ -32,11 +36,22 @@ constexpr int ORHS = 4;            // right-hand sides of a^T / w^T staged per p
 constexpr int OT_THREADS = 256;    // points of a workgroup of loo_terms_kernel, one per thread
 
 // ---- per-point terms -----------------------------------------------------------------------------------------------------------
+// model blockIdx.y: Kinv + b sK, at + b sAt, qt + b sQt, its workgroups' sums at partials + b gridDim.x, var / rootd [batch, n]
+struct LooTermStrides { int64_t sK, sAt, sQt; };
+
 __global__ __launch_bounds__(OT_THREADS) void loo_terms_kernel(const double* __restrict__ Kinv, int64_t ldk, const double* __restrict__ at,
                                                                int64_t ldat, int64_t n, int dy, double* __restrict__ partials,
                                                                double* __restrict__ qt, int64_t ldqt, double* __restrict__ var,
-                                                               double* __restrict__ rootd) {
+                                                               double* __restrict__ rootd, LooTermStrides st) {
   __shared__ double red[OT_THREADS / 64];
+  if (const int64_t b = blockIdx.y) {
+    Kinv += b * st.sK;
+    at += b * st.sAt;
+    partials += b * gridDim.x;
+    if (qt) qt += b * st.sQt;
+    if (var) var += b * n;
+    if (rootd) rootd += b * n;
+  }
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t i = (int64_t)blockIdx.x * OT_THREADS + tid;
   double term = 0.0;
@@ -64,9 +79,12 @@ __global__ __launch_bounds__(OT_THREADS) void loo_terms_kernel(const double* __r
 
 static_assert(OT_THREADS == 256, "the workgroup's sums are combined as (w0 + w1) + (w2 + w3)");
 
-// value[0] = offset + the `count` workgroup sums, in a fixed strided order and the same tree
+// value[0] = offset + the `count` workgroup sums, in a fixed strided order and the same tree (model blockIdx.y: its `count` sums
+// and value[b])
 __global__ __launch_bounds__(256) void loo_sum_kernel(const double* __restrict__ partials, int64_t count, double offset, double* __restrict__ value) {
   __shared__ double red[4];
+  partials += (int64_t)blockIdx.y * count;
+  value += blockIdx.y;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   double a = 0.0;
   for (int64_t i = threadIdx.x; i < count; i += 256) a += partials[i];
@@ -108,10 +126,16 @@ __device__ __forceinline__ void loo_load_lower(const double* __restrict__ M, int
 }
 
 // ---- S = P diag(sqrt d), both triangles ----------------------------------------------------------------------------------------
+// (model blockIdx.y: Kinv + b sK, rootd + b n, S + b sS)
 __global__ __launch_bounds__(256) void loo_scale_kernel(const double* __restrict__ Kinv, int64_t ldk, const double* __restrict__ rootd, int n,
-                                                        double* __restrict__ S, int64_t lds) {
+                                                        double* __restrict__ S, int64_t lds, int64_t sK, int64_t sS) {
   __shared__ double T[OT][OT + 1];
   __shared__ double rrow[OT], rcol[OT];
+  if (const int64_t b = blockIdx.y) {
+    Kinv += b * sK;
+    rootd += b * n;
+    S += b * sS;
+  }
   int ti, tj;
   loo_lower_tile(blockIdx.x, ti, tj);
   const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
@@ -164,6 +188,20 @@ struct LooGradArgs {
   int n, d, nls, dy, nout;
 };
 
+// model b of a lock-step launch: its operands b strides on (sX = 0: shared points), its own variance and length scales, its tiles'
+// partials after those of the models before it
+struct LooGradStrides { int64_t sX, sQ, sAt, sWt; };
+
+__device__ __forceinline__ void loo_model(LooGradArgs& p, const LooGradStrides& st, int64_t b) {
+  p.X += b * st.sX;
+  p.variance += b;
+  p.ls += b * p.nls;
+  p.Q += b * st.sQ;
+  p.at += b * st.sAt;
+  p.wt += b * st.sWt;
+  p.work += b * (int64_t)gridDim.x * p.nout;
+}
+
 struct LooStage {
   double xs[ODC][OT];     // row points, [coordinate][point], pre-multiplied by 1 / ell
   double ys[ODC][OT];     // column points
@@ -200,7 +238,8 @@ __device__ __forceinline__ void loo_fragments(const LooStage& S, int dd, int tx,
 }
 
 template <int KIND>
-__global__ __launch_bounds__(256) void loo_grad_kernel(LooGradArgs p) {
+__global__ __launch_bounds__(256) void loo_grad_kernel(LooGradArgs p, LooGradStrides st) {
+  if (const int64_t b = blockIdx.y) loo_model(p, st, b);
   __shared__ __attribute__((aligned(16))) LooStage S;
   __shared__ double arow[ORHS][OT], acol[ORHS][OT], wrow[ORHS][OT], wcol[ORHS][OT];
   __shared__ double red[256];
@@ -336,10 +375,13 @@ __global__ __launch_bounds__(256) void loo_grad_kernel(LooGradArgs p) {
   if (tid == 0) out[1 + p.nls] = tt;
 }
 
-// out[k] = sum over the tiles' partials, in a fixed order
+// out[k] = sum over the tiles' partials, in a fixed order (model blockIdx.y of a lock-step launch: its nblocks x nout partials and
+// its row of out)
 __global__ __launch_bounds__(256) void loo_grad_reduce_kernel(const double* __restrict__ partial, int64_t nblocks, int nout, double* __restrict__ out) {
   __shared__ double red[256];
   const int k = blockIdx.x, tid = threadIdx.x;
+  partial += (int64_t)blockIdx.y * nblocks * nout;
+  out += (int64_t)blockIdx.y * nout;
   double s = 0.0;
   for (int64_t b = tid; b < nblocks; b += 256) s += partial[b * nout + k];
   red[tid] = s;
@@ -352,6 +394,74 @@ __global__ __launch_bounds__(256) void loo_grad_reduce_kernel(const double* __re
 }
 
 static int64_t loo_tiles(int64_t n) { return (n + OT - 1) / OT; }
+
+constexpr int LOO_MAX_BATCH = 65535;      // the model index is a grid's y dimension: larger batches go out in several launches
+
+// the extent of a [rows, n] row-major block with leading dimension ld, in doubles: the least stride between two models' blocks
+static int64_t loo_extent(int64_t rows, int64_t n, int64_t ld) { return rows <= 0 || n <= 0 ? 0 : (rows - 1) * ld + n; }
+
+// ---- the launches: `batch` models per call (validated by the entry points; n > 0) ------------------------------------------------
+static int loo_terms_launch(hipStream_t s, int batch, int64_t n, int dy, const double* Kinv, int64_t ldk, int64_t sK, const double* at,
+                            int64_t ldat, int64_t sAt, double* work, double* qt, int64_t ldqt, int64_t sQt, double* var, double* rootd,
+                            double* value) {
+  const int64_t blocks = (n + OT_THREADS - 1) / OT_THREADS;
+  const double offset = -0.5 * (double)n * (double)dy * 1.83787706640934548356;      // log(2 pi)
+  const LooTermStrides st = {sK, sAt, sQt};
+  for (int64_t z0 = 0; z0 < batch; z0 += LOO_MAX_BATCH) {
+    const unsigned nb = (unsigned)std::min<int64_t>(LOO_MAX_BATCH, batch - z0);
+    double* wz = work + z0 * blocks;
+    hipLaunchKernelGGL(loo_terms_kernel, dim3((unsigned)blocks, nb), dim3(OT_THREADS), 0, s, Kinv + z0 * sK, ldk, at + z0 * sAt, ldat, n, dy, wz,
+                       qt ? qt + z0 * sQt : nullptr, ldqt, var ? var + z0 * n : nullptr, rootd ? rootd + z0 * n : nullptr, st);
+    GPN_LAUNCH_CHECK();
+    if (value) {
+      hipLaunchKernelGGL(loo_sum_kernel, dim3(1, nb), dim3(256), 0, s, wz, blocks, offset, value + z0);
+      GPN_LAUNCH_CHECK();
+    }
+  }
+  return GPN_OK;
+}
+
+static int loo_scale_launch(hipStream_t s, int batch, int64_t n, const double* Kinv, int64_t ldk, int64_t sK, const double* rootd, double* S,
+                            int64_t lds, int64_t sS) {
+  const int64_t t = loo_tiles(n), nblocks = t * (t + 1) / 2;
+  if (nblocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
+  for (int64_t z0 = 0; z0 < batch; z0 += LOO_MAX_BATCH) {
+    const unsigned nb = (unsigned)std::min<int64_t>(LOO_MAX_BATCH, batch - z0);
+    hipLaunchKernelGGL(loo_scale_kernel, dim3((unsigned)nblocks, nb), dim3(256), 0, s, Kinv + z0 * sK, ldk, rootd + z0 * n, (int)n, S + z0 * sS, lds,
+                       sK, sS);
+    GPN_LAUNCH_CHECK();
+  }
+  return GPN_OK;
+}
+
+// p: model 0's operands; work holds batch x tiles x nout partials, out [batch, nout]
+static int loo_grad_launch(hipStream_t s, int kind, int batch, LooGradArgs p, const LooGradStrides& st, double* out) {
+  const int64_t n = p.n, t = loo_tiles(n), nblocks = t * (t + 1) / 2;
+  if (nblocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
+  const double nn = (double)n;
+  for (int64_t z0 = 0; z0 < batch; z0 += LOO_MAX_BATCH) {
+    const unsigned nb = (unsigned)std::min<int64_t>(LOO_MAX_BATCH, batch - z0);
+    LooGradArgs q = p;
+    q.X += z0 * st.sX; q.variance += z0; q.ls += z0 * p.nls; q.Q += z0 * st.sQ; q.at += z0 * st.sAt; q.wt += z0 * st.sWt;
+    q.work += z0 * nblocks * p.nout;
+    const dim3 grid((unsigned)nblocks, nb);
+    int rec = -1;
+    if (profile_on()) rec = profile_begin(s, 8.0 * (double)nb * (0.5 * nn * (nn + 1.0) + nn * p.d), PROF_GRAD);
+    switch (kind) {
+      case GPN_RBF: hipLaunchKernelGGL(loo_grad_kernel<GPN_RBF>, grid, dim3(256), 0, s, q, st); break;
+      case GPN_MATERN52: hipLaunchKernelGGL(loo_grad_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, q, st); break;
+      case GPN_MATERN32: hipLaunchKernelGGL(loo_grad_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, q, st); break;
+      case GPN_EXP: hipLaunchKernelGGL(loo_grad_kernel<GPN_EXP>, grid, dim3(256), 0, s, q, st); break;
+      case GPN_SQDIST: hipLaunchKernelGGL(loo_grad_kernel<GPN_SQDIST>, grid, dim3(256), 0, s, q, st); break;
+      default: hipLaunchKernelGGL(loo_grad_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, q, st); break;
+    }
+    if (rec >= 0) profile_end(s, rec);
+    GPN_LAUNCH_CHECK();
+    hipLaunchKernelGGL(loo_grad_reduce_kernel, dim3((unsigned)p.nout, nb), dim3(256), 0, s, q.work, nblocks, p.nout, out + z0 * p.nout);
+    GPN_LAUNCH_CHECK();
+  }
+  return GPN_OK;
+}
 
 }  // namespace gpn
 
@@ -380,14 +490,38 @@ extern "C" int gpn_loo_terms(void* stream, int64_t n, int dy, const double* Kinv
     if (value) GPN_HIP_CHECK(hipMemsetAsync(value, 0, sizeof(double), s));
     return GPN_OK;
   }
-  hipLaunchKernelGGL(loo_terms_kernel, dim3((unsigned)blocks), dim3(OT_THREADS), 0, s, Kinv, ldk, at, ldat, n, dy, work, qt, ldqt, var, rootd);
-  GPN_LAUNCH_CHECK();
-  if (value) {
-    const double offset = -0.5 * (double)n * (double)dy * 1.83787706640934548356;      // log(2 pi)
-    hipLaunchKernelGGL(loo_sum_kernel, dim3(1), dim3(256), 0, s, work, blocks, offset, value);
-    GPN_LAUNCH_CHECK();
+  return loo_terms_launch(s, 1, n, dy, Kinv, ldk, 0, at, ldat, 0, work, qt, ldqt, 0, var, rootd, value);
+}
+
+extern "C" int64_t gpn_loo_terms_batched_work_bytes(int64_t n, int batch) {
+  if (batch < 1) return 0;
+  return (int64_t)batch * gpn_loo_terms_work_bytes(n);
+}
+
+extern "C" int gpn_loo_terms_batched(void* stream, int batch, int64_t n, int dy, const double* Kinv, int64_t ldk, int64_t sK,
+                                     const double* at, int64_t ldat, int64_t sAt, double* work, int64_t work_bytes, double* qt,
+                                     int64_t ldqt, int64_t sQt, double* var, double* rootd, double* value) {
+  if (batch < 1) return -2;
+  if (n < 0) return -3;
+  if (dy < 1) return -4;
+  if (!Kinv) return -5;
+  if (ldk < n) return -6;
+  if (batch > 1 && sK < loo_extent(n, n, ldk)) return -7;
+  if (!at) return -8;
+  if (ldat < n) return -9;
+  if (batch > 1 && sAt < loo_extent(dy, n, ldat)) return -10;
+  if (n > 0 && !work) return -11;
+  const int64_t blocks = (n + OT_THREADS - 1) / OT_THREADS;
+  if (blocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
+  if (work_bytes < gpn_loo_terms_batched_work_bytes(n, batch)) return -12;
+  if (qt && ldqt < n) return -14;
+  if (qt && batch > 1 && sQt < loo_extent(dy, n, ldqt)) return -15;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (n == 0) {
+    if (value) GPN_HIP_CHECK(hipMemsetAsync(value, 0, (size_t)batch * sizeof(double), s));
+    return GPN_OK;
   }
-  return GPN_OK;
+  return loo_terms_launch(s, batch, n, dy, Kinv, ldk, sK, at, ldat, sAt, work, qt, ldqt, sQt, var, rootd, value);
 }
 
 extern "C" int gpn_loo_scale(void* stream, int64_t n, const double* Kinv, int64_t ldk, const double* rootd, double* S, int64_t lds) {
@@ -398,11 +532,22 @@ extern "C" int gpn_loo_scale(void* stream, int64_t n, const double* Kinv, int64_
   if (!S) return -6;
   if (lds < n) return -7;
   if (n == 0) return GPN_OK;
-  const int64_t t = loo_tiles(n), nblocks = t * (t + 1) / 2;
-  if (nblocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
-  hipLaunchKernelGGL(loo_scale_kernel, dim3((unsigned)nblocks), dim3(256), 0, static_cast<hipStream_t>(stream), Kinv, ldk, rootd, (int)n, S, lds);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  return loo_scale_launch(static_cast<hipStream_t>(stream), 1, n, Kinv, ldk, 0, rootd, S, lds, 0);
+}
+
+extern "C" int gpn_loo_scale_batched(void* stream, int batch, int64_t n, const double* Kinv, int64_t ldk, int64_t sK, const double* rootd,
+                                     double* S, int64_t lds, int64_t sS) {
+  if (batch < 1) return -2;
+  if (n < 0 || n > 0x7fffffff) return -3;
+  if (!Kinv) return -4;
+  if (ldk < n) return -5;
+  if (batch > 1 && sK < loo_extent(n, n, ldk)) return -6;
+  if (!rootd) return -7;
+  if (!S) return -8;
+  if (lds < n) return -9;
+  if (batch > 1 && sS < loo_extent(n, n, lds)) return -10;
+  if (n == 0) return GPN_OK;
+  return loo_scale_launch(static_cast<hipStream_t>(stream), batch, n, Kinv, ldk, sK, rootd, S, lds, sS);
 }
 
 extern "C" int64_t gpn_loo_grad_work_bytes(int64_t n, int nls) {
@@ -439,23 +584,47 @@ extern "C" int gpn_loo_grad(void* stream, int kind, const double* X, int64_t n, 
     GPN_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)p.nout * sizeof(double), s));
     return GPN_OK;
   }
-  const int64_t t = loo_tiles(n), nblocks = t * (t + 1) / 2;
-  if (nblocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
-  const dim3 grid((unsigned)nblocks);
-  const double nn = (double)n;
-  int rec = -1;
-  if (profile_on()) rec = profile_begin(s, 8.0 * (0.5 * nn * (nn + 1.0) + nn * d), PROF_GRAD);
-  switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL(loo_grad_kernel<GPN_RBF>, grid, dim3(256), 0, s, p); break;
-    case GPN_MATERN52: hipLaunchKernelGGL(loo_grad_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, p); break;
-    case GPN_MATERN32: hipLaunchKernelGGL(loo_grad_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, p); break;
-    case GPN_EXP: hipLaunchKernelGGL(loo_grad_kernel<GPN_EXP>, grid, dim3(256), 0, s, p); break;
-    case GPN_SQDIST: hipLaunchKernelGGL(loo_grad_kernel<GPN_SQDIST>, grid, dim3(256), 0, s, p); break;
-    default: hipLaunchKernelGGL(loo_grad_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, p); break;
+  return loo_grad_launch(s, kind, 1, p, LooGradStrides{0, 0, 0, 0}, out);
+}
+
+extern "C" int64_t gpn_loo_grad_batched_work_bytes(int64_t n, int nls, int batch) {
+  if (batch < 1) return 0;
+  return (int64_t)batch * gpn_loo_grad_work_bytes(n, nls);
+}
+
+extern "C" int gpn_loo_grad_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d, const double* variance,
+                                    const double* length_scales, int nls, const double* Q, int64_t ldq, int64_t sQ, const double* at,
+                                    int64_t ldat, int64_t sAt, const double* wt, int64_t ldwt, int64_t sWt, int dy, double* work,
+                                    int64_t work_bytes, double* out) {
+  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;
+  if (batch < 1) return -3;
+  if (!X) return -4;
+  if (n < 0 || n > 0x7fffffff) return -6;
+  if (d <= 0) return -7;
+  if (sX != 0 && sX < n * d) return -5;
+  if (!variance) return -8;
+  if (!length_scales) return -9;
+  if (nls != 1 && nls != d) return -10;
+  if (!Q) return -11;
+  if (ldq < n) return -12;
+  if (batch > 1 && sQ < loo_extent(n, n, ldq)) return -13;
+  if (!at) return -14;
+  if (ldat < n) return -15;
+  if (dy < 1) return -20;
+  if (batch > 1 && sAt < loo_extent(dy, n, ldat)) return -16;
+  if (!wt) return -17;
+  if (ldwt < n) return -18;
+  if (batch > 1 && sWt < loo_extent(dy, n, ldwt)) return -19;
+  if (n > 0 && !work) return -21;
+  if (work_bytes < gpn_loo_grad_batched_work_bytes(n, nls, batch)) return -22;
+  if (!out) return -23;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  LooGradArgs p = {};
+  p.X = X; p.variance = variance; p.ls = length_scales; p.Q = Q; p.ldq = ldq; p.at = at; p.ldat = ldat; p.wt = wt; p.ldwt = ldwt;
+  p.work = work; p.n = (int)n; p.d = d; p.nls = nls; p.dy = dy; p.nout = 2 + nls;
+  if (n == 0) {
+    GPN_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)batch * p.nout * sizeof(double), s));
+    return GPN_OK;
   }
-  if (rec >= 0) profile_end(s, rec);
-  GPN_LAUNCH_CHECK();
-  hipLaunchKernelGGL(loo_grad_reduce_kernel, dim3((unsigned)p.nout), dim3(256), 0, s, p.work, nblocks, p.nout, out);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  return loo_grad_launch(s, kind, batch, p, LooGradStrides{sX, sQ, sAt, sWt}, out);
 }

@@ -20,6 +20,7 @@ class GroupKey(NamedTuple):
     nls: int                          # number of length scales (1 or d: ARD)
     device: torch.device
     sizes: Optional[tuple] = None     # a RAGGED group: every model's own number of rows
+    objective: str = "lml"            # what the group's models fit (GPR.objective): "loo" groups run _ops.BatchedGPRLooLik
 
 
 # Lock-step buffers reused between calls (a search calls batched_log_likelihood / batched_loss_and_grad once per optimiser
@@ -33,7 +34,10 @@ BATCH_BUFFER_MAX_BYTES = 48 << 30
 
 
 def _held_bytes():
-    return sum(v["fb"].nbytes() for v in _BATCH_BUFFERS.values() if "fb" in v)
+    # (a leave-one-out group keeps its right-hand sides, Q and the sweep's partials beside its FactorBatch; the inversion's workspace
+    #  is the FactorBatch's _backward_work)
+    return sum(v["fb"].nbytes() for v in _BATCH_BUFFERS.values() if "fb" in v) + \
+        sum(8 * v[name].numel() for v in _BATCH_BUFFERS.values() for name in _ops.LOO_HOLDER_BUFFERS if v.get(name) is not None)
 
 
 def _batch_holder(key):
@@ -173,6 +177,30 @@ def _lockstep_groups(models, for_grad=False):
                 # (all of one size after all: the ordinary equal-size group)
                 out.append((common._replace(shape=(nmax,) + common.shape, sizes=sizes if len(set(sizes)) > 1 else None), chunk))
             at = end
+    return out
+
+
+def _loo_groups(models):
+    """[(GroupKey, indices)] of the GPR(objective="loo") models that can share one lock-step evaluation (_ops.BatchedGPRLooLik): GPR's
+    own loss / loo_log_predictive over a native stationary kernel on the GPU, of a size _loo_lockstep.supported() admits, grouped by
+    (kernel kind, X's shape, dy, ARD or not, device) -- equal shapes only, no ragged pooling -- and split into chunks that fit the
+    device's free memory; singletons stay sequential.  The key's objective field is "loo": it selects the node and keeps the cached
+    buffers apart from those of an LML group of the same shape."""
+    from . import _loo_lockstep
+    from .gpr import GPR
+    groups = {}
+    for i, m in enumerate(models):
+        if not isinstance(m, GPR) or m.objective != "loo":
+            continue
+        if type(m).loss is not GPR.loss or type(m)._loss is not GPR._loss or type(m).loo_log_predictive is not GPR.loo_log_predictive:
+            continue                                     # a subclass that evaluates differently takes its own path
+        k = m._stationary()
+        if k is None or not m.X.is_cuda or not _loo_lockstep.supported(m.X.shape[0]):
+            continue
+        groups.setdefault(_group_key(m)._replace(objective="loo"), []).append(i)
+    out = []
+    for key, g in groups.items():
+        out += _chunks(key, g, _capacity(_loo_lockstep.per_model_bytes(key.shape[0], key.dy, key.nls), key.device, held=_held_bytes()))
     return out
 
 
@@ -480,13 +508,16 @@ def _has_priors(ms):
 
 
 def _plan_groups(models):
-    """the grouping of batched_loss_and_grad for a list of models: [(lock-step groups), (expression groups), (sparse groups),
+    """the grouping of batched_loss_and_grad for a list of models: [(lock-step groups: the LML's and, with objective == "loo" in their key, the leave-one-out ones), (expression groups), (sparse groups),
     (LaplaceGP and EPGP groups: their keys begin with "laplace" / "ep")] with each group's "has priors" flag.  Shapes, kernels and priors do not change while a search runs:
     multi_start_optimize plans ONCE and hands the plan to every iteration (the grouping walks every model's parameters and, for composite kernels, rebuilds their
     expression programs: host time that a small-N iteration would spend several times over)."""
     _place_all(models)
-    models = [m if getattr(m, "objective", "lml") == "lml" else None for m in models]   # another objective: that model's own loss(), sequentially
-    return ([(key, g, _has_priors([models[i] for i in g])) for key, g in _lockstep_groups(models)],
+    # leave-one-out models: groups of their own (_loo_groups), travelling in the first list with objective == "loo" in their key;
+    # the other groupings do not see them (the ones no LOO group takes: their own loss(), sequentially)
+    loo = [(key, g, _has_priors([models[i] for i in g])) for key, g in _loo_groups(models)]
+    models = [m if getattr(m, "objective", "lml") == "lml" else None for m in models]
+    return ([(key, g, _has_priors([models[i] for i in g])) for key, g in _lockstep_groups(models)] + loo,
             [(key, g, progs, _has_priors([models[i] for i in g])) for key, g, progs in _expression_groups(models)],
             [(key, g, _has_priors([models[i] for i in g])) for key, g in _vfe_groups(models)],
             [(key, g, _has_priors([models[i] for i in g])) for key, g in _laplace_groups(models) + _ep_groups(models)])
@@ -520,7 +551,9 @@ def batched_loss_and_grad(models, _plan=None):
     transforms and their chain rule are one small launch per parameter kind.  Each model's loss AND gradients are
     BIT-IDENTICAL to its own `loss(); backward()`; a model whose factorisation fails is replayed alone through the jitter
     ladder; parameters with priors add their model's own log_prior() (model.py:158-197); sizes that refine the quadratic
-    form refine it per model.  Composite / dense-K kernels and singletons take the sequential path.  Equal-shape LaplaceGP models
+    form refine it per model.  Composite / dense-K kernels and singletons take the sequential path.  Equal-shape
+    GPR(objective="loo") models run in lock step too (_loo_groups, _ops.BatchedGPRLooLik: they travel in the plan's first list with
+    objective == "loo" in their key), each model's loss and gradients bit-identical to its own evaluation.  Equal-shape LaplaceGP models
     run their mode searches, evidences and closed-form gradients in lock step too (_laplace_groups, models/_laplace_lockstep.py),
     each model's loss, gradients, warm-start mode and newton_stats bit-identical to its own evaluation; so do equal-shape EPGP
     models (_ep_groups, models/_ep_lockstep.py): loss, gradients, sites and ep_stats bit-identical per model."""
@@ -531,6 +564,10 @@ def batched_loss_and_grad(models, _plan=None):
         X, R, n_of = _group_data(ms, differentiable=True, key=key)
         var, ls, nz = _group_hypers(ms, differentiable=True)
         holder = _batch_holder((key, len(ms)))
+        if key.objective == "loo":
+            # leave-one-out restarts / kernel choices of one shape: L_LOO, its closed-form gradients and -w in lock step
+            _group_loss_and_grad(_ops.BatchedGPRLooLik.apply(X, R, var, ls, nz, key.kind, holder), ms, g, priors, out, True)
+            continue
         if n_of is not None:
             holder["sizes"] = key.sizes
         _group_loss_and_grad(_ops.BatchedGPRLogLik.apply(X, R, var, ls, nz, key.kind, holder, n_of), ms, g, priors, out, True)

@@ -494,7 +494,10 @@ int gpn_lml_backward_batched(void* stream, int kind, int batch, const double* X,
  * callers whose dKyy/dtheta is not a native stationary kind: composite kernels (kernels.py:286-306) sweep their own
  * expression against these with gpn_kernel_expr_grad, model by model (gptorch_amd/_expr.py BatchedExprLogLik).
  * gpn_lml_kinv_layout: out4 = {leading dimension, offset of Kyy^-1 [n, ld], offset of a^T [dy, ld], doubles from one model's
- * block of `work` to the next}; work: gpn_lml_kinv_batched_work_bytes bytes. */
+ * block of `work` to the next}; work: gpn_lml_kinv_batched_work_bytes bytes.
+ * U = L^-T itself (upper triangular, [gpn_factor_rows(n, 0), ld], its padding zero) is left at OFFSET 0 of every model's block:
+ * the layout call does not report it because it is always 0.  Leave-one-out's w = P q = (q^T U) U^T reads it there
+ * (_ops.BatchedGPRLooLik). */
 int gpn_lml_kinv_layout(int64_t n, int dy, int64_t* out4);
 int64_t gpn_lml_kinv_batched_work_bytes(int64_t n, int dy, int batch);
 int gpn_lml_kinv_batched(void* stream, int batch, int64_t n, const double* A, int64_t lda, int64_t sA,
@@ -869,6 +872,25 @@ int64_t gpn_loo_grad_work_bytes(int64_t n, int nls);
 int gpn_loo_grad(void* stream, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
                  int nls, const double* Q, int64_t ldq, const double* at, int64_t ldat, const double* wt, int64_t ldwt, int dy,
                  double* work, int64_t work_bytes, double* out);
+/* The same three for `batch` models of one shape in LOCK STEP: the SAME kernels with the model on the grid's y dimension (the single
+ * entry points are their batch = 1 calls), model b at pointer + b * stride (strides in doubles; for batch > 1 a stride covers at
+ * least the block it steps over; sX = 0: shared points), variance[b], length_scales + b * nls, var / rootd [batch, n], value [batch],
+ * out [batch, 2 + nls]; the workspace's partial sums are per model, in the single call's order.  Every row carries the BITS of the
+ * single call on that model alone; nothing outside [n, n], [dy, n] or [n] of a model's block is written; a batch above 65535 goes
+ * out in several launches.  n == 0: value / out are zeroed, nothing is launched.
+ * work_bytes >= gpn_loo_terms_batched_work_bytes(n, batch) = batch * gpn_loo_terms_work_bytes(n), and
+ * gpn_loo_grad_batched_work_bytes(n, nls, batch) = batch * gpn_loo_grad_work_bytes(n, nls). */
+int64_t gpn_loo_terms_batched_work_bytes(int64_t n, int batch);
+int gpn_loo_terms_batched(void* stream, int batch, int64_t n, int dy, const double* Kinv, int64_t ldk, int64_t sK,
+                          const double* at, int64_t ldat, int64_t sAt, double* work, int64_t work_bytes, double* qt,
+                          int64_t ldqt, int64_t sQt, double* var, double* rootd, double* value);
+int gpn_loo_scale_batched(void* stream, int batch, int64_t n, const double* Kinv, int64_t ldk, int64_t sK, const double* rootd,
+                          double* S, int64_t lds, int64_t sS);
+int64_t gpn_loo_grad_batched_work_bytes(int64_t n, int nls, int batch);
+int gpn_loo_grad_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d, const double* variance,
+                         const double* length_scales, int nls, const double* Q, int64_t ldq, int64_t sQ, const double* at,
+                         int64_t ldat, int64_t sAt, const double* wt, int64_t ldwt, int64_t sWt, int dy, double* work,
+                         int64_t work_bytes, double* out);
 
 /* ---- optional launch profiler (bench.py's roofline legs) ---------------------- */
 /* While enabled, every contraction / assembly / gradient-sweep / leaf launch of this library is bracketed by two HIP events
