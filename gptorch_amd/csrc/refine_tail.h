@@ -7,26 +7,33 @@
 
 namespace gpn {
 
-// ---- double-double accumulation (explicitly rounded intrinsics: never contracted into FMAs by the compiler) ----
+// ---- double-double accumulation ----
+// Every operation below must round on its own.  hipcc contracts a * b + c into an FMA by default (-ffp-contract=fast-honor-pragmas),
+// and HIP's __dadd_rn / __dsub_rn / __dmul_rn are plain operators in an inline function, which that contraction sees through: with
+// them, `acc.hi + p` and `p - bb` in dd_fma became fma(a, b, acc.hi) and fma(a, b, -bb), which counts the product's rounding error
+// twice and left Kyy a_hat with an error of eps |Kyy| |a_hat| instead of eps^2.  So: plain operators under `fp contract(off)`.
 struct dd { double hi, lo; };
 __device__ __forceinline__ void two_sum(double a, double b, double& s, double& e) {
-  s = __dadd_rn(a, b);
-  const double bb = __dsub_rn(s, a);
-  e = __dadd_rn(__dsub_rn(a, __dsub_rn(s, bb)), __dsub_rn(b, bb));
+#pragma clang fp contract(off)
+  s = a + b;
+  const double bb = s - a;
+  e = (a - (s - bb)) + (b - bb);
 }
 __device__ __forceinline__ void dd_fma(dd& acc, double a, double b) {        // acc += a * b, error-free product and sum
-  const double p = __dmul_rn(a, b);
-  const double ep = __fma_rn(a, b, -p);
+#pragma clang fp contract(off)
+  const double p = a * b;
+  const double ep = __builtin_fma(a, b, -p);
   double s, es;
   two_sum(acc.hi, p, s, es);
   acc.hi = s;
-  acc.lo = __dadd_rn(acc.lo, __dadd_rn(es, ep));
+  acc.lo = acc.lo + (es + ep);
 }
 __device__ __forceinline__ void dd_add(dd& acc, const dd x) {
+#pragma clang fp contract(off)
   double s, e;
   two_sum(acc.hi, x.hi, s, e);
   acc.hi = s;
-  acc.lo = __dadd_rn(acc.lo, __dadd_rn(e, x.lo));
+  acc.lo = acc.lo + (e + x.lo);
 }
 
 constexpr int RT = 64;        // tile edge of the residual kernels (= kmat.hip's KT, kexpr.hip's ET)

@@ -90,6 +90,11 @@ class DistGPR(GPR):
             if prog is None or any(t.type == _native.TERM_WHITE for t in prog.terms):
                 raise NotImplementedError("DistGPR assembles its tiles with the native stationary kernels (Rbf, Matern52, ...) or with "
                                           "Sum / Product trees over native leaves (no White leaf)")
+            if not prog.grad_supported(self.X.shape[1]):
+                # the expression sweeps keep one accumulator per input in registers: without this check the first backward fails
+                # with a NativeError on every rank, mid-collective
+                raise NotImplementedError("DistGPR evaluates a Sum / Product tree with the fused expression kernels only: per-input "
+                                          "parameters (ARD length scales, Linear's variances) need input_dim <= 16; got %d" % self.X.shape[1])
             self._prog = prog
         self._tile, self._grid, self._tile_ops = int(tile), grid, tile_ops
         self._schedule = schedule        # panel exchange: "bcast" | "mesh" (dist.BlockCyclicGP); None = GPN_DIST_SCHEDULE / "bcast"

@@ -1,5 +1,6 @@
 """
-TEST INFRASTRUCTURE ONLY -- an extended-precision reference for the stationary kinds.
+TEST INFRASTRUCTURE ONLY -- an extended-precision reference for the stationary kinds and for Sum / Product trees
+over them, Linear, Constant / Bias and White.
 
 The CPU oracle (oracle/gp_oracle.py) restates the reference's algorithm, Gram-trick distances included
 (r^2 = |a|^2 + |b|^2 - 2 a.b, util.py:73-88 in the reference).  Next to a repeated point that leaves
@@ -123,19 +124,23 @@ def Kdiag(X, variance):
     return np.full(np.shape(X)[0], LD(variance), dtype=LD)
 
 
-def kernel_param_grads(kind, X, X2, variance, length_scales, W, ard):
-    """d sum(W * K(X, X2)) / d(log variance, log ell) -> (g_var [1], g_ls [d or 1])."""
+def kernel_param_grads(kind, X, X2, variance, length_scales, W, ard, r2=None):
+    """d sum(W * K(X, X2)) / d(log variance, log ell) -> (g_var [1], g_ls [d or 1]).  r2: scaled_sqdist(X, X2, length_scales) if the
+    caller has it already."""
     X = ld(X)
     X2 = X if X2 is None else ld(X2)
     W = ld(W)
     ls = _ls(length_scales, X.shape[1])
-    Km, B = k_of_r2(kind, scaled_sqdist(X, X2, ls), variance)
+    r2 = scaled_sqdist(X, X2, ls) if r2 is None else r2
+    Km, B = k_of_r2(kind, r2, variance)
     WB = W * B
+    if not ard:                                        # sum_d s_d = r^2: one pass instead of d
+        return np.array([np.sum(W * Km)]), np.array([np.sum(WB * r2)])
     g = np.empty(X.shape[1], dtype=LD)
     for c in range(X.shape[1]):
         t = (X[:, c:c + 1] - X2[None, :, c]) / ls[c]
         g[c] = np.sum(WB * t * t)
-    return np.array([np.sum(W * Km)]), (g if ard else np.array([g.sum()]))
+    return np.array([np.sum(W * Km)]), g
 
 
 def kernel_point_grads(kind, X, X2, variance, length_scales, W):
@@ -153,6 +158,151 @@ def kernel_point_grads(kind, X, X2, variance, length_scales, W):
         gX[:, c] = -np.sum(WB * t, axis=1)
         gX2[:, c] = np.sum(WB * t, axis=0)
     return (gX + gX2) if sym else (gX, gX2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# expressions: Sum / Product trees (kernels.py:286-306) over stationary leaves, Linear (238-265), Constant / Bias (95-105)
+# and White (83-92)
+# ---------------------------------------------------------------------------------------------------------------------
+# A spec is the tree in sum-of-products form: a list of groups, each a list of leaf dicts
+#     {"id": key, "type": "stationary" | "linear" | "constant" | "white", "kind": one of KINDS (stationary only),
+#      "variance": a number (linear: or one per input), "length_scales": a number or one per input (stationary only), "ard": bool}
+# K = sum over groups of the elementwise product of the group's leaves.  Leaves with one id are ONE leaf (one set of
+# parameters) standing in several groups, as in (a + b) * c = a c + b c.
+def leaf(id, type, kind=None, variance=1.0, length_scales=None, ard=False):
+    return {"id": id, "type": type, "kind": kind, "variance": variance, "length_scales": length_scales, "ard": ard}
+
+
+def expand_tree(tree):
+    """("+", a, b) / ("*", a, b) over leaf dicts -> spec, by distributivity (groups in the order a b-major expansion gives:
+    (a + b) * (c + d) = a c + a d + b c + b d)."""
+    if isinstance(tree, dict):
+        return [[tree]]
+    op, a, b = tree
+    a, b = expand_tree(a), expand_tree(b)
+    return a + b if op == "+" else [x + y for x in a for y in b]
+
+
+def spec_leaves(spec):
+    """the distinct leaves in first-visit order."""
+    out = []
+    for g in spec:
+        for l in g:
+            if all(l["id"] != q["id"] for q in out):
+                out.append(l)
+    return out
+
+
+def split_instances(spec):
+    """the same expression with every leaf instance a leaf of its own (ids (id, group, position)): its parameter gradients
+    are the per-instance gradients of `spec`."""
+    return [[dict(l, id=(l["id"], gi, ti)) for ti, l in enumerate(g)] for gi, g in enumerate(spec)]
+
+
+def _lin_v(l, d):
+    v = np.atleast_1d(ld(l["variance"]))
+    return v if v.size == d else np.full(d, v[0], dtype=LD)
+
+
+def leaf_K(l, X, X2, r2=None):
+    """one leaf's K(X, X2) (X2 None: K(X)) in long double (r2: a stationary leaf's scaled_sqdist, if the caller has it)."""
+    X = ld(X)
+    sym = X2 is None
+    X2 = X if sym else ld(X2)
+    n, m = X.shape[0], X2.shape[0]
+    t = l["type"]
+    if t == "stationary":
+        return k_of_r2(l["kind"], scaled_sqdist(X, X2, l["length_scales"]) if r2 is None else r2, l["variance"])[0]
+    if t == "linear":
+        return (X * _lin_v(l, X.shape[1])) @ X2.T
+    if t == "constant":
+        return np.full((n, m), LD(l["variance"]), dtype=LD)
+    if t == "white":
+        # kernels.py:83-92: the variance on the diagonal of K(X); identically zero for K(X, X2), whatever X2 holds
+        return LD(l["variance"]) * np.eye(n, dtype=LD) if sym else np.zeros((n, m), dtype=LD)
+    raise ValueError(t)
+
+
+def leaf_Kdiag(l, X):
+    X = ld(X)
+    if l["type"] == "linear":
+        return np.sum(X * X * _lin_v(l, X.shape[1]), 1)
+    return np.full(X.shape[0], LD(l["variance"]), dtype=LD)      # kernels.py:67-80, 174-179 (White included)
+
+
+def leaf_param_grads(l, X, X2, W, r2=None):
+    """d sum(W * K_leaf(X, X2)) / d(log variance(s), log ell) -> (g_var, g_ls); g_ls is empty for a leaf without length scales."""
+    X = ld(X)
+    sym = X2 is None
+    X2 = X if sym else ld(X2)
+    W = ld(W)
+    t = l["type"]
+    none = np.zeros(0, dtype=LD)
+    if t == "stationary":
+        return kernel_param_grads(l["kind"], X, X2, l["variance"], l["length_scales"], W, l["ard"], r2=r2)
+    if t == "linear":
+        v = _lin_v(l, X.shape[1])
+        g = np.array([v[c] * np.sum(W * np.outer(X[:, c], X2[:, c])) for c in range(X.shape[1])], dtype=LD)
+        return (g if np.size(l["variance"]) > 1 or l["ard"] else np.array([g.sum()])), none
+    if t == "constant":
+        return np.array([LD(l["variance"]) * np.sum(W)]), none
+    if t == "white":
+        return np.array([LD(l["variance"]) * np.trace(W) if sym else LD(0)]), none
+    raise ValueError(t)
+
+
+def expr_K(spec, X, X2=None):
+    """the long-double value of the expression."""
+    total = None
+    for g in spec:
+        prod = None
+        for l in g:
+            Kl = leaf_K(l, X, X2)
+            prod = Kl if prod is None else prod * Kl
+        total = prod if total is None else total + prod
+    return total
+
+
+def expr_Kdiag(spec, X):
+    total = None
+    for g in spec:
+        prod = None
+        for l in g:
+            Kl = leaf_Kdiag(l, X)
+            prod = Kl if prod is None else prod * Kl
+        total = prod if total is None else total + prod
+    return total
+
+
+def expr_param_grads(spec, X, X2, W, with_K=False):
+    """d sum(W * K(X, X2)) / d log theta for every parameter of every distinct leaf, in closed form:
+    {id: (g_var, g_ls)}.  A leaf instance sees the weight W * prod(other terms of its group); instances of one leaf add up.
+    with_K: -> (gradients, expr_K(spec, X, X2)) from the same pass."""
+    W = ld(W)
+    out, total = {}, None
+    for g in spec:
+        r2s = [scaled_sqdist(X, X2, l["length_scales"]) if l["type"] == "stationary" else None for l in g]
+        Ks = [leaf_K(l, X, X2, r2) for l, r2 in zip(g, r2s)]
+        for ti, l in enumerate(g):
+            Wt = W.copy()
+            for ui, Ku in enumerate(Ks):
+                if ui != ti:
+                    Wt = Wt * Ku
+            gv, gl = leaf_param_grads(l, X, X2, Wt, r2s[ti])
+            if l["id"] in out:
+                out[l["id"]] = (out[l["id"]][0] + gv, out[l["id"]][1] + gl)
+            else:
+                out[l["id"]] = (gv, gl)
+        prod = Ks[0]
+        for Ku in Ks[1:]:
+            prod = prod * Ku
+        total = prod if total is None else total + prod
+    return (out, total) if with_K else out
+
+
+def flat_grads(spec, grads):
+    """{id: (g_var, g_ls)} -> the non-empty gradient vectors in leaf order (variance, then length scales)."""
+    return [g for l in spec_leaves(spec) for g in grads[l["id"]] if np.size(g)]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -206,18 +356,23 @@ def solve_upper_t(L, B):
 # GPR (gpr.py:47-117 of the reference) in long double
 # ---------------------------------------------------------------------------------------------------------------------
 class GPRRef:
-    """Exact GPR with a stationary kernel, a Gaussian likelihood and a constant mean, every intermediate in long
+    """Exact GPR with a stationary kernel or an expression, a Gaussian likelihood and a constant mean, every intermediate in long
     double.  Parameters are the constrained values; gradients are w.r.t. their logs (ExpTransform) and, for the mean,
     w.r.t. the value itself."""
 
-    def __init__(self, x, y, kind, variance, length_scales, noise, ARD=False, mean=None):
+    def __init__(self, x, y, kind, variance=None, length_scales=None, noise=None, ARD=False, mean=None):
+        """kind: a stationary kind's name with (variance, length_scales, ARD) -- or an expression spec (expr_K), which carries its
+        own parameters: GPRRef(x, y, spec, noise=..., mean=...)."""
         self.X, self.Y = ld(x), ld(y)
         self.n, self.dy = self.Y.shape
-        self.kind, self.ARD = kind, ARD
-        self.var, self.noise = LD(variance), LD(noise)
-        self.ls = _ls(length_scales, self.X.shape[1])
+        self.noise = LD(noise)
+        if isinstance(kind, str):
+            self.spec = [[leaf("k", "stationary", kind, LD(variance), _ls(length_scales, self.X.shape[1]), ARD)]]
+            self.kind, self.ARD, self.var, self.ls = kind, ARD, LD(variance), self.spec[0][0]["length_scales"]
+        else:
+            self.spec = kind
         self.mean = np.zeros(self.dy, dtype=LD) if mean is None else ld(mean)
-        self.Kf = K(kind, self.X, None, self.var, self.ls)
+        self.Kf = expr_K(self.spec, self.X, None)
         self.Kyy = self.Kf + self.noise * np.eye(self.n, dtype=LD)
         self.L = cholesky(self.Kyy)
         self.R = self.Y - self.mean
@@ -231,22 +386,23 @@ class GPRRef:
         return -self.lml()
 
     def loss_grads(self):
-        """d loss / d(log variance, log ell [d or 1], log noise, mean [dy]) with
+        """d loss / d(log variance, log ell [d or 1], log noise, mean [dy]) -- for an expression: every distinct leaf's
+        (log variance(s), log ell) in leaf order (flat_grads), then log noise and the mean -- with
         G = 1/2 (a a^T - dy Kyy^-1), a = Kyy^-1 (y - m):  dLML/dtheta = sum(G * dK/dtheta), dLML/dm = sum_i a_i."""
         a = solve_upper_t(self.L, self.alpha)
         Li = solve_lower(self.L, np.eye(self.n, dtype=LD))
         G = LD(0.5) * (a @ a.T - self.dy * np.einsum("ki,kj->ij", Li, Li))
-        g_var, g_ls = kernel_param_grads(self.kind, self.X, None, self.var, self.ls, G, self.ARD)
+        gk = flat_grads(self.spec, expr_param_grads(self.spec, self.X, None, G))
         g_noise = self.noise * np.trace(G)
-        return [-g_var, -g_ls, -np.array([g_noise]), -a.sum(0)]
+        return [-g for g in gk] + [-np.array([g_noise]), -a.sum(0)]
 
     def predict_f(self, x_new, diag=True):
         xs = ld(x_new)
-        A = solve_lower(self.L, K(self.kind, self.X, xs, self.var, self.ls))
+        A = solve_lower(self.L, expr_K(self.spec, self.X, xs))
         mean = A.T @ self.alpha + self.mean
         if diag:
-            return mean, np.repeat((Kdiag(xs, self.var) - np.sum(A * A, 0))[:, None], self.dy, 1)
-        return mean, K(self.kind, xs, None, self.var, self.ls) - A.T @ A
+            return mean, np.repeat((expr_Kdiag(self.spec, xs) - np.sum(A * A, 0))[:, None], self.dy, 1)
+        return mean, expr_K(self.spec, xs, None) - A.T @ A
 
     def predict_y(self, x_new, diag=True):
         mean, v = self.predict_f(x_new, diag)
@@ -279,11 +435,87 @@ def direct_kernel_K(kind, X, X2, variance, length_scales):
     raise ValueError(kind)
 
 
+def direct_expr_K(spec, X, X2=None, params=None):
+    """expr_K in torch fp64 with direct_kernel_K for the stationary leaves -- the plain fp64 evaluation whose error against
+    the long-double value is e64.  params: {id: (variance tensor, length-scale tensor or None)} (differentiable); default: the
+    spec's own values as float64 tensors."""
+    sym = X2 is None
+    X2 = X if sym else X2
+    n, m = X.shape[0], X2.shape[0]
+    total = None
+    for g in spec:
+        prod = None
+        for l in g:
+            v, ls = params[l["id"]] if params is not None else leaf_tensors(l)
+            t = l["type"]
+            if t == "stationary":
+                Kl = direct_kernel_K(l["kind"], X, X2, v, ls)
+            elif t == "linear":
+                Kl = (X * v) @ X2.t()
+            elif t == "constant":
+                Kl = v.expand(n, m)
+            else:
+                Kl = torch.diag(v.expand(n)) if sym else v * torch.zeros(n, m, dtype=X.dtype)
+            prod = Kl if prod is None else prod * Kl
+        total = prod if total is None else total + prod
+    return total
+
+
+def leaf_tensors(l, log=False, grad=False):
+    """(variance, length scales or None) of a leaf as float64 tensors (their logs with log=True).  float64 explicitly:
+    torch.tensor([0.8]) is float32 and would put 4e-8 into every "fp64" value."""
+    def t(a):
+        a = np.atleast_1d(np.asarray(a, dtype=np.float64))
+        return torch.tensor(np.log(a) if log else a, dtype=torch.float64, requires_grad=grad)
+    return t(l["variance"]), (None if l["length_scales"] is None else t(l["length_scales"]))
+
+
 class DirectGPR(orc.GPROracle):
-    """orc.GPROracle with K(X, X2) by direct differences (everything else: the reference's op chain in fp64)."""
+    """orc.GPROracle with K(X, X2) by direct differences (everything else: the reference's op chain in fp64).  kind: a stationary
+    kind's name, or an expression spec (DirectGPR(x, y, kind=spec, noise=..., mean=...))."""
+
+    def __init__(self, x, y, kind="Rbf", variance=1.0, length_scales=1.0, noise=None, ARD=False, mean=None):
+        self.spec = None
+        if isinstance(kind, str):
+            super().__init__(x, y, kind=kind, variance=variance, length_scales=length_scales, noise=noise, ARD=ARD, mean=mean)
+            return
+        super().__init__(x, y, kind="Rbf", noise=noise, mean=mean)
+        self.spec = kind
+        self.raw = {l["id"]: leaf_tensors(l, log=True, grad=True) for l in spec_leaves(kind)}
+
+    def parameters(self):
+        """an expression: every distinct leaf's (raw variance(s), raw ell) in leaf order (GPRRef.loss_grads), then the raw noise"""
+        if self.spec is None:
+            return super().parameters()
+        return [p for l in spec_leaves(self.spec) for p in self.raw[l["id"]] if p is not None] + [self.raw_noise]
 
     def K(self, X, X2=None):
-        return direct_kernel_K(self.kind, X, X2, self.raw_variance.exp(), self.raw_length_scales.exp())
+        if self.spec is None:
+            return direct_kernel_K(self.kind, X, X2, self.raw_variance.exp(), self.raw_length_scales.exp())
+        return direct_expr_K(self.spec, X, X2, {i: (v.exp(), None if l is None else l.exp()) for i, (v, l) in self.raw.items()})
+
+    def Kdiag(self, X):
+        if self.spec is None:
+            return orc.kernel_Kdiag(X, self.raw_variance.exp())
+        total = 0.0
+        for g in self.spec:
+            prod = 1.0
+            for l in g:
+                v = self.raw[l["id"]][0].exp()
+                prod = prod * ((X * X * v).sum(1) if l["type"] == "linear" else v.expand(X.shape[0]))
+            total = total + prod
+        return total
+
+    def predict_f(self, x_new, diag=True):
+        """gpr.py:88-117 (GPROracle.predict_f with this class's Kdiag)."""
+        x_new = torch.as_tensor(np.asarray(x_new), dtype=orc.DTYPE)
+        L = orc.cholesky(self.compute_kyy(self.X))
+        A = orc.trtrs(self.K(self.X, x_new), L)
+        V = orc.trtrs(self.Y - self._mean(self.X), L)
+        mean_f = A.t() @ V + self._mean(x_new)
+        if diag:
+            return mean_f, (self.Kdiag(x_new) - (A * A).sum(0))[:, None].expand_as(mean_f)
+        return mean_f, self.K(x_new) - A.t() @ A
 
     def loss_grads_with_mean(self):
         """loss and d loss / d(raw variance, raw ell, raw noise, mean) by autograd."""

@@ -352,3 +352,12 @@ def test_dist_gpr_rejects_what_the_grid_cannot_assemble(device):
     x, y = rng.make_regression(100, 3, 1, seed=0)
     with pytest.raises(NotImplementedError):
         DistGPR(x, y, kernels.Matern52(3) + kernels.White(3, variance=0.05))
+    # per-input parameters beyond the 16 inputs of the expression sweeps: refused at construction, not in the first backward
+    x17, y17 = rng.make_regression(100, 17, 1, seed=0)
+    for k in (kernels.Rbf(17, length_scales=np.ones(17), ARD=True) + kernels.Constant(17), kernels.Matern52(17) + kernels.Linear(17)):
+        assert k.fused_program() is not None
+        with pytest.raises(NotImplementedError):
+            DistGPR(x17, y17, k)
+    x16, y16 = rng.make_regression(100, 16, 1, seed=0)
+    DistGPR(x16, y16, kernels.Rbf(16, length_scales=np.ones(16), ARD=True) + kernels.Constant(16))      # 16 inputs: accepted
+    DistGPR(x17, y17, kernels.Rbf(17) + kernels.Constant(17))                                           # no per-input parameter: any d

@@ -157,3 +157,135 @@ def test_the_oracle_fails_the_exp_tolerance():
     with torch.no_grad():
         assert np.max(np.abs(np.diag(o.K(o.X).numpy()) - 1.3)) > 1e3 * xr.FLOOR["K"]
     assert np.all(np.diag(r.Kf) == LD(1.3))                      # v exp(-1e-20): v to long-double precision
+
+
+# ---- expressions: Sum / Product trees over stationary leaves, Linear, Constant and White ----------------------------
+def _expr_spec(d):
+    """rbf * m52_ard + lin_ard + white + const, and the rbf leaf once more in  rbf * white * exp_ard  (a leaf in two groups,
+    White inside a product)."""
+    rbf = xr.leaf("rbf", "stationary", "Rbf", 1.3, 1.4)
+    m52 = xr.leaf("m52", "stationary", "Matern52", 0.9, np.linspace(0.8, 1.7, d), ard=True)
+    lin = xr.leaf("lin", "linear", variance=np.linspace(0.3, 0.9, d), ard=True)
+    wh = xr.leaf("wh", "white", variance=0.25)
+    cst = xr.leaf("c", "constant", variance=0.4)
+    ex = xr.leaf("exp", "stationary", "Exp", 0.7, np.linspace(1.1, 2.0, d), ard=True)
+    return [[rbf, m52], [lin], [wh], [cst], [rbf, wh, ex]]
+
+
+def _mp_expr(spec, x, x2, sym):
+    """the expression for one pair of points at the working precision of mpmath (inputs: float64, exact)."""
+    total = mpmath.mpf(0)
+    for g in spec:
+        prod = mpmath.mpf(1)
+        for l in g:
+            v = [_mpf(t) for t in np.atleast_1d(l["variance"])]
+            if l["type"] == "stationary":
+                ls = [_mpf(t) for t in np.atleast_1d(l["length_scales"])]
+                r2 = sum(((mpmath.mpf(float(a)) - mpmath.mpf(float(b))) / ls[c % len(ls)]) ** 2 for c, (a, b) in enumerate(zip(x, x2)))
+                prod *= _mp_k(l["kind"], r2, v[0])
+            elif l["type"] == "linear":
+                prod *= sum(mpmath.mpf(float(a)) * v[c % len(v)] * mpmath.mpf(float(b)) for c, (a, b) in enumerate(zip(x, x2)))
+            elif l["type"] == "constant":
+                prod *= v[0]
+            else:
+                prod *= v[0] if sym else 0
+        total += prod
+    return total
+
+
+def test_expression_value_against_mpmath():
+    """expr_K of a tree with a product of two stationary leaves, Linear-ARD, White (alone and inside a product) and Constant,
+    entry by entry at 30 digits: K(X) (White on the diagonal only, also where rows repeat) and K(X, X2)."""
+    n, m, d = 6, 5, 3
+    x, x2 = rng.normal(11, (n, d)), rng.normal(12, (m, d))
+    x[4] = x[1]                                         # a repeated row: off the diagonal, no White
+    x2[2] = x[0]
+    spec = _expr_spec(d)
+    Ks, Kx = xr.expr_K(spec, x, None), xr.expr_K(spec, x, x2)
+    with mpmath.workdps(30):
+        for i in range(n):
+            for j in range(n):
+                want = _mp_expr(spec, x[i], x[j], i == j)
+                assert abs(_mpf(Ks[i, j]) - want) <= 2e-17 * max(1, abs(want)), (i, j)
+            for j in range(m):
+                want = _mp_expr(spec, x[i], x2[j], False)
+                assert abs(_mpf(Kx[i, j]) - want) <= 2e-17 * max(1, abs(want)), (i, j)
+    assert Ks[1, 4] == Ks[4, 1] and Ks[1, 1] - Ks[1, 4] > 0.25          # White: the diagonal only
+    assert xr.abs_err(xr.expr_Kdiag(spec, x), np.diag(Ks)) < 1e-17          # Linear's sum(x x v) rounds unlike (x v) x^T
+
+
+def test_white_is_zero_across_two_sets_even_of_the_same_points():
+    x = rng.normal(13, (7, 2))
+    wh = xr.leaf("wh", "white", variance=0.25)
+    assert np.count_nonzero(xr.leaf_K(wh, x, x.copy())) == 0
+    assert np.array_equal(xr.leaf_K(wh, x, None), LD(0.25) * np.eye(7, dtype=LD))
+    spec = [[wh, xr.leaf("rbf", "stationary", "Rbf", 1.3, 1.4)]]
+    assert np.count_nonzero(xr.expr_K(spec, x, x.copy())) == 0
+    g = xr.expr_param_grads(spec, x, x.copy(), rng.normal(14, (7, 7)))
+    assert all(np.count_nonzero(v) == 0 for pair in g.values() for v in pair)
+
+
+@pytest.mark.parametrize("sym", [True, False])
+def test_expression_gradients_against_central_differences(sym):
+    """expr_param_grads (closed form, d/d log theta) against central differences of sum(W * expr_K) in long double: a leaf in
+    two groups, White inside a product, Linear-ARD, and the same spec with one shared Linear variance."""
+    n, m, d = 9, 7, 3
+    x, x2 = rng.normal(21, (n, d)), (None if sym else rng.normal(22, (m, d)))
+    W = rng.normal(23, (n, n if sym else m))
+    for spec in (_expr_spec(d), [[xr.leaf("lin1", "linear", variance=0.6), xr.leaf("per", "stationary", "Periodic", 0.8, 2.5)]]):
+        leaves = xr.spec_leaves(spec)
+        g = xr.expr_param_grads(spec, x, x2, W)
+
+        def value(lid, field, c, step):
+            mod = [[dict(l, **{field: np.atleast_1d(xr.ld(l[field])) * np.exp(step * (np.arange(np.size(l[field])) == c))})
+                    if l["id"] == lid else l for l in grp] for grp in spec]
+            return np.sum(xr.ld(W) * xr.expr_K(mod, x, x2))
+
+        h = LD("1e-5")
+        checked = 0
+        for l in leaves:
+            for field, got in zip(("variance", "length_scales"), g[l["id"]]):
+                assert np.size(got) == (0 if l[field] is None else np.size(l[field]))
+                for c in range(np.size(got)):
+                    fd = (value(l["id"], field, c, h) - value(l["id"], field, c, -h)) / (2 * h)
+                    assert abs(fd - got[c]) < 1e-9 * max(1, abs(got[c])), (l["id"], field, c, fd, got[c])
+                    checked += 1
+        assert checked == sum(np.size(l["variance"]) + (0 if l["length_scales"] is None else np.size(l["length_scales"])) for l in leaves)
+
+
+def test_gpr_reference_accepts_an_expression():
+    """GPRRef / DirectGPR over a spec: the closed-form gradients against central differences of the reference's own loss, and
+    the fp64 direct evaluation (autograd through direct_expr_K) agreeing with it in loss, gradients and predictions; a
+    one-leaf spec reproduces the (kind, variance, length_scales) constructor."""
+    n, d, dy = 24, 3, 2
+    x, y = rng.make_regression(n, d, dy, seed=5)
+    spec = [[xr.leaf("lin", "linear", variance=np.linspace(0.3, 0.9, d), ard=True)], [xr.leaf("rbf", "stationary", "Rbf", 1.2, 1.5)],
+            [xr.leaf("c", "constant", variance=0.4)]]
+    mean = np.array([0.2, -0.1])
+    r = xr.GPRRef(x, y, spec, noise=0.05, mean=mean)
+    g = r.loss_grads()
+    assert [np.size(v) for v in g] == [d, 1, 1, 1, 1, dy]
+    h = LD("1e-5")
+    for lid, field, c, got in [("lin", "variance", 1, g[0][1]), ("rbf", "variance", 0, g[1][0]), ("rbf", "length_scales", 0, g[2][0]),
+                               ("c", "variance", 0, g[3][0])]:
+        def loss(step):
+            mod = [[dict(l, **{field: np.atleast_1d(xr.ld(l[field])) * np.exp(step * (np.arange(np.size(l[field])) == c))})
+                    if l["id"] == lid else l for l in grp] for grp in spec]
+            return xr.GPRRef(x, y, mod, noise=0.05, mean=mean).loss()
+        fd = (loss(h) - loss(-h)) / (2 * h)
+        assert abs(fd - got) < 1e-9 * max(1, abs(got)), (lid, field, fd, got)
+    dg = xr.DirectGPR(x, y, kind=spec, noise=0.05, mean=mean)
+    l64, g64 = dg.loss_grads_with_mean()
+    assert l64.dtype == torch.float64 and all(t.dtype == torch.float64 for t in g64)
+    assert xr.rel_err(l64.item(), r.loss()) < 1e-12
+    assert len(g64) == len(g) and all(xr.rel_err(a, b) < 1e-10 for a, b in zip(g64, g))
+    xs = np.concatenate([rng.normal(6, (5, d)), x[:2]])
+    for f in ("predict_f", "predict_y"):
+        for diag in (True, False):
+            with torch.no_grad():
+                om, ov = getattr(dg, f)(xs, diag=diag)
+            rm, rv = getattr(r, f)(xs, diag=diag)
+            assert xr.abs_err(om, rm) < 1e-11 and xr.abs_err(ov, rv) < 1e-11, (f, diag)
+    one = xr.GPRRef(x, y, [[xr.leaf("k", "stationary", "Matern32", 1.3, 1.4)]], noise=0.05)
+    old = xr.GPRRef(x, y, "Matern32", 1.3, 1.4, 0.05)
+    assert one.loss() == old.loss() and all(np.array_equal(a, b) for a, b in zip(one.loss_grads(), old.loss_grads()))
