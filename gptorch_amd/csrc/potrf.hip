@@ -83,7 +83,8 @@ static void potrf_rec(Ctx& c, double* A, int64_t n, int64_t e, int64_t col0) {
 // and one large K = PW contraction for everything right of the panel at its end.  The two
 // streams are joined by events (fork/join, so the whole call can also be captured in a
 // hipGraph); no data-dependent host logic.  The upper triangle inside the panel's diagonal
-// square receives finite garbage from the rectangular updates: nothing reads it (the leaf
+// square receives garbage from the rectangular updates (finite if it was on entry; gpnative.h:
+// "not read, unspecified on exit" -- tests/test_gpu_factor_xref.py fills it with NaN): nothing reads it (the leaf
 // masks j > i on load, every other consumer uses blocks strictly below the diagonal blocks
 // or winv).
 struct Aux {

@@ -91,7 +91,10 @@ int gpn_pack_rhs(void* stream, const double* Y, const double* M, int64_t n, int 
  * Replaces functions.cholesky's torch.cholesky call (functions.py:46-47; the
  * jitter ladder of functions.py:20-43 stays in the Python shell and replays on
  * info>0).  In-place lower factorisation of the n x n top-left block of the
- * factor buffer A; the strict upper triangle is neither read nor written.
+ * factor buffer A; the strict upper triangle is not read and is UNSPECIFIED on
+ * exit (the panel drivers' rectangular updates run over the diagonal squares:
+ * it may hold anything, NaN included if it did on entry -- Factor.lower() /
+ * gpn_copy_matrix(tril = 1) mask it).
  * `winv` (gpn_winv_bytes(n)) receives the inverses of the 128x128 diagonal blocks
  * of L and must be kept with L for the solves below.  e extra rows are carried
  * (see header comment).  *info must be 0 on entry. */

@@ -215,7 +215,8 @@ def test_functions_are_differentiable(device, n):
             ).abs().max().item() < 1e-10
 
 
-@pytest.mark.parametrize("n,e", [(1152, 0), (2500, 3), (8320, 1), (9001, 2), (16640, 2), (20608, 5)])
+# ((20480, 2) and (20608, 4): the E = 2 and E = 4 instantiations of extra_rows_update_kernel, which only run from XR_MIN_N = 20480)
+@pytest.mark.parametrize("n,e", [(1152, 0), (2500, 3), (8320, 1), (9001, 2), (16640, 2), (20608, 5), (20480, 2), (20608, 4)])
 def test_factorisation_drivers_agree(device, n, e):
     """the nested-panel driver (default: 256-wide inner panels in 1024-wide outer ones below N = 20480, 512 in 2048 above;
     from N = 20480 the extra rows' share of an outer panel's update as dot products on the aux stream, below that a thin
