@@ -561,6 +561,18 @@ def gemm_nt_batched(A, B, M, N, K, batch, sA, sB, C, alpha=1.0, beta=0.0, lower=
     return C
 
 
+def gemm_nt_batched_scaled(A, B, M, N, K, batch, sA, sB, C, alphas, beta=0.0, lower=False, tri=0):
+    """gemm_nt_batched with one scale per problem from device memory: C[z] = alphas[z]*A_z*B_z^T + beta*C[z] (alphas: `batch`
+    contiguous fp64 on the operands' device), per problem bit-identical to gemm_nt(alpha=alphas[z])."""
+    _req(A, B, C, alphas)
+    if alphas.numel() < batch or not alphas.is_contiguous():
+        raise RuntimeError("gemm_nt_batched_scaled: alphas must hold `batch` contiguous values")
+    st = _native.lib().gpn_gemm_nt_batched_scaled(_stream(A.device), M, N, K, _ptr(alphas), _ptr(A), A.stride(0), sA, _ptr(B), B.stride(0), sB,
+                                                  beta, _ptr(C), C.stride(1), C.stride(0), 1 if lower else 0, tri, batch)
+    _native.check(st, "gpn_gemm_nt_batched_scaled")
+    return C
+
+
 def transpose(src):
     _req(src)
     src = _c(src.detach())

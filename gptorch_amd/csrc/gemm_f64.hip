@@ -40,8 +40,13 @@ __global__ __launch_bounds__(64 * (BM / WM) * (BN / WN), ((BM / WM) * (BN / WN) 
 }
 
 // Switches (gpn_common.h: constants in the product library, per-thread variables behind gpn_debug_set_gemm_variant /
-// gpn_debug_set_thin_tiles in the tools' build) -- forcing one tile shape for a launch is how tests/test_gpu_gemm.py holds every
-// shape against the reference product (and against each other: bit-identical).
+// gpn_debug_set_thin_tiles in the tools' build) -- forcing one tile shape for a launch is how the tests hold every shape against
+// the reference product: tests/test_gpu_gemm.py on exact integers (fragment maps, tile walks; any summation order is exact
+// there), tests/test_gpu_gemm_xref.py on full-mantissa data against a long-double product -- and against each other.  Every
+// variant (0, 1, 3..11: all three shipped shapes, register staging, plain and pipelined loops, thin tiles on and off, K-clipped
+// or not) sums an entry's terms in the same order, K-step by K-step, k = {0,2,4,6} then {1,3,5,7} of each group of 8, and gives
+// the same BITS on full-mantissa data; the lock-step drivers' "bit-identical per model" rests on that (a batch picks another
+// tile shape than one model).  A change to the K order of one shape breaks it: test_every_tile_shape_gives_the_same_bits.
 GPN_SWITCH int g_gemm_variant = 0;  // 0 = the shipped dispatch, 1 = register staging, 3..11 = forced tile shapes
 GPN_SWITCH int g_thin_tiles = 1;    // the thin-tile path (reaches the kernels through GemmArgs)
 GPN_SWITCH int g_smem_pad = 0;      // extra dynamic LDS per workgroup (KiB): lowers the occupancy

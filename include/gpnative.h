@@ -181,10 +181,19 @@ int gpn_lml_reduce(void* stream, const double* A, int64_t n, int64_t e, int64_t 
  * lower != 0: square case M == N, only tiles on/below the diagonal are computed
  * and entries with j > i are not written (SYRK-style trailing update).
  * Requirements: K % 16 == 0; lda, ldb % 2 == 0; A, B 16-byte aligned; rows of A
- * (B) readable up to round_up(M,16) (round_up(N,16)). */
+ * (B) readable up to round_up(M,16) (round_up(N,16)); what those padding rows hold is
+ * never used (NaN included: the result has the same bits as with zeros there).
+ * beta == 0: C is not read (it may hold NaN or Inf).  A NaN or Inf in row i of A reaches
+ * row i of C only, one in row j of B column j only.  Subnormal operands, products and
+ * sums are kept (gradual underflow, nothing is flushed to zero).  Every tile shape the
+ * launcher may pick sums an entry's K terms in the same order: the result does not depend
+ * on the problem's size class or on `batch` (tests/test_gpu_gemm_xref.py). */
 /* tri: structure hints that clip the K range per tile (operand entries in the clipped
- * range MUST be zero): A_UPPER: A[i,k] = 0 for k < i; A_LOWER: A[i,k] = 0 for k > i
- * (to tile granularity: k >= 128*ceil((i+1)/128)); likewise for B with its row index j. */
+ * range MUST be zero): A_UPPER: A[i,k] = 0 for EVERY k < i; A_LOWER: A[i,k] = 0 for EVERY
+ * k > i; likewise for B with its row index j.  Strict triangles: the clip follows the edge
+ * of the tile the launcher picks (32, 64 or 128 rows), so an operand that is only zero
+ * from some coarser boundary on silently loses terms.  With the flags the result has the
+ * bits of the same call without them. */
 enum { GPN_TRI_A_UPPER = 1, GPN_TRI_A_LOWER = 2, GPN_TRI_B_UPPER = 4, GPN_TRI_B_LOWER = 8 };
 /* lower == 2 ("trapezoid", M >= N, tri == 0): the N x N top square is treated as with lower == 1 and the
  * (M - N) x N rectangle below it is computed whole -- one tile column of a block-cyclic trailing update including
