@@ -175,6 +175,14 @@ SIGNATURES = {
     "gpn_loo_grad_batched_work_bytes": (c_int64, [c_int64, c_int, c_int]),
     "gpn_loo_grad_batched": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64,
                                      c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    # k-fold cross-validation of the exact GP in closed form (csrc/kfold.hip)
+    "gpn_kfold_gather": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64,
+                                 c_void_p, c_int64, c_int64]),
+    "gpn_kfold_columns_work_bytes": (c_int64, [c_int64, c_int, c_int64]),
+    "gpn_kfold_columns": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64]),
+    "gpn_kfold_weights_work_bytes": (c_int64, [c_int, c_int64, c_int]),
+    "gpn_kfold_terms": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p,
+                                c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p]),
 }
 LIK_PROBIT, LIK_LOGIT, LIK_POISSON, LIK_STUDENT_T = 0, 1, 2, 3   # include/gpnative.h GPN_LIK_*
 LIK_ROWS_PER_GROUP = 256                                        # GPN_LIK_ROWS_PER_GROUP

@@ -1499,4 +1499,259 @@ class DenseLooLik(torch.autograd.Function):
                 (go * G.diagonal().sum()).reshape(1) if ctx.needs_input_grad[2] else None)
 
 
+# ----------------------------------------------------------------------------
+# k-fold cross-validation in closed form (GPR(objective="kfold")): csrc/kfold.hip
+# ----------------------------------------------------------------------------
+KFOLD_PAD_FACTOR = 4     # a partition is refused when k * round_up(m_max, 16) > KFOLD_PAD_FACTOR * round_up(n, 16) (FoldTable)
+
+
+class FoldTable:
+    """A partition of range(n) into k >= 2 folds as the kernels read it: off [k + 1] and idx [n], int32 on `device` (fold f =
+    idx[off[f] : off[f + 1]], in the order given), m_max the largest fold.  folds: an int k (np.array_split(np.arange(n), k):
+    contiguous blocks in data order, no shuffling) or a sequence of integer index arrays; anything that is not a partition with
+    at least two non-empty folds raises ValueError.  Every fold is padded to m_max: a partition with k * round_up(m_max, 16) >
+    4 round_up(n, 16) (all-singleton folds among them) would more than quadruple an N x N buffer -- [round_up(n, 16), k *
+    round_up(m_max, 16)] is the column buffer of the backward -- and raises NotImplementedError.  (Both sides count padded rows:
+    against the bare n the 16-row granule alone would refuse every partition of fewer than 8 points.)"""
+
+    def __init__(self, folds, n, device=None):
+        import numpy as np
+        n = int(n)
+        if folds is None:
+            raise ValueError("objective='kfold' needs folds: an int k >= 2 or a sequence of index arrays that partition range(n)")
+        if isinstance(folds, (int, np.integer)) and not isinstance(folds, bool):
+            k = int(folds)
+            if k < 2 or k > n:
+                raise ValueError("folds: an int k must satisfy 2 <= k <= n = %d; got %d" % (n, k))
+            parts = np.array_split(np.arange(n), k)
+        else:
+            try:
+                parts = [np.asarray(p.detach().cpu() if torch.is_tensor(p) else p) for p in folds]
+            except TypeError:
+                raise ValueError("folds must be an int or a sequence of integer index arrays; got %r" % (folds,))
+            if len(parts) < 2:
+                raise ValueError("folds: at least two folds are needed; got %d" % len(parts))
+            for p in parts:
+                if p.ndim != 1 or p.size == 0:
+                    raise ValueError("folds: every fold is a non-empty 1-D index array")
+                if p.dtype.kind not in "iu":
+                    raise ValueError("folds: index arrays must hold integers; got dtype %s" % p.dtype)
+            flat = np.concatenate(parts).astype(np.int64)
+            if flat.size != n or flat.min() < 0 or flat.max() >= n or np.unique(flat).size != n:
+                raise ValueError("folds must partition range(%d): every index exactly once" % n)
+        sizes = [int(p.size) for p in parts]
+        self.n, self.k, self.sizes, self.m_max = n, len(parts), tuple(sizes), max(sizes)
+        if self.k * round_up(self.m_max, 16) > KFOLD_PAD_FACTOR * round_up(n, 16):
+            raise NotImplementedError(
+                "folds: padding %d folds to the largest (%d points) would more than quadruple an N x N buffer at n = %d; "
+                "for (nearly) singleton folds use objective=\"loo\"" % (self.k, self.m_max, n))
+        self.parts = [p.astype(np.int64) for p in parts]
+        self._off = torch.tensor(np.concatenate([[0], np.cumsum(sizes)]), dtype=torch.int32)
+        self._idx = torch.tensor(np.concatenate(self.parts), dtype=torch.int32)
+        self._on = {}
+        if device is not None:
+            self.on(device)
+
+    def on(self, device):
+        """(off, idx) on `device` (copied once per device)"""
+        device = torch.device(device)
+        if device not in self._on:
+            self._on[device] = (self._off.to(device), self._idx.to(device))
+        return self._on[device]
+
+
+def kfold_gather(Kinv, at, n, dy, table, fb):
+    """gpn_kfold_gather: P[I_f, I_f], the identity padding and a_I^T into the k ZEROED factor buffers of the FactorBatch fb"""
+    _req(Kinv, at)
+    at, ldat = _rhs_rows(at, n)
+    off, idx = table.on(Kinv.device)
+    st = _native.lib().gpn_kfold_gather(_stream(Kinv.device), n, dy, _ptr(Kinv), Kinv.stride(0), _ptr(at), ldat, table.k, _ptr(off), _ptr(idx),
+                                        table.m_max, _ptr(fb.A), fb.ld, fb.sA)
+    _native.check(st, "gpn_kfold_gather")
+    return fb
+
+
+def kfold_columns(Kinv, n, table):
+    """gpn_kfold_columns: P[:, I_f] as full columns -> [k, round_up(n, 16), round_up(m_max, 16)], zero padded"""
+    _req(Kinv)
+    off, idx = table.on(Kinv.device)
+    C = torch.empty(table.k, round_up(n, 16), round_up(table.m_max, 16), dtype=torch.float64, device=Kinv.device)
+    st = _native.lib().gpn_kfold_columns(_stream(Kinv.device), n, _ptr(Kinv), Kinv.stride(0), table.k, _ptr(off), _ptr(idx), table.m_max,
+                                         _ptr(C), C.stride(1), C.stride(0))
+    _native.check(st, "gpn_kfold_columns")
+    return C
+
+
+def kfold_factorise(fb):
+    """the k gathered fold blocks factorised in lock step (gpn_potrf_lower_batched: beta_f^T = a_I^T L_f^-T in the extra rows) ->
+    (out3 [k, 3] of gpn_lml_reduce_batched, U [k, rows, ld] = L_f^-T of gpn_trtri_upper_batched).  fb.info is left on the device."""
+    lib = _native.lib()
+    dev = fb.A.device
+    fb.info.zero_()
+    st = lib.gpn_potrf_lower_batched(_stream(dev), _ptr(fb.A), fb.n, fb.e, fb.ld, fb.sA, _ptr(fb.winv), fb.sW, _ptr(fb.info), fb.batch)
+    _native.check(st, "gpn_potrf_lower_batched")
+    st = lib.gpn_lml_reduce_batched(_stream(dev), _ptr(fb.A), fb.n, fb.e, fb.ld, fb.sA, _ptr(fb.out), fb.batch)
+    _native.check(st, "gpn_lml_reduce_batched")
+    U = zeros(fb.batch * fb.rows, fb.ld, dev)
+    S = zeros(fb.batch * fb.rows, fb.ld, dev) if fb.n > 2 * LEAF else None
+    st = lib.gpn_trtri_upper_batched(_stream(dev), _ptr(fb.A), fb.n, fb.ld, fb.sA, _ptr(fb.winv), fb.sW, _ptr(U), fb.ld, fb.sA,
+                                     _ptr(S), fb.ld, fb.sA, fb.batch)
+    _native.check(st, "gpn_trtri_upper_batched")
+    if S is not None:
+        S.record_stream(torch.cuda.current_stream(dev))
+    return fb.out, U
+
+
+def kfold_terms(table, n, dy, fb, U, out3=None, info=None, qt=None, want_q=True, want_var=True, want_w=True, want_value=True):
+    """gpn_kfold_terms -> (qt [dy, n] = (y - mu)^T and var [n] in DATA order, Wt [k, round_up(m_max + dy, 16), round_up(m_max, 16)]
+    = W_f^T, value 0-dim = L_kfold); an output that is not wanted is None.  qt given: a row-major buffer q^T is written into."""
+    lib = _native.lib()
+    dev = fb.A.device
+    off, idx = table.on(dev)
+    k, m = table.k, table.m_max
+
+    def new(want, *shape):
+        return torch.empty(shape, dtype=torch.float64, device=dev) if want else None
+
+    if qt is None:
+        qt = new(want_q, dy, n)
+    var, value = new(want_var, n), new(want_value)
+    Wt = zeros(k * round_up(m + dy, 16), round_up(m, 16), dev) if want_w else None
+    st = lib.gpn_kfold_terms(_stream(dev), n, dy, k, _ptr(off), _ptr(idx), m, _ptr(U), fb.ld, fb.sA, _ptr(fb.A), fb.ld, fb.sA,
+                             _ptr(out3), _ptr(info), _ptr(qt), 0 if qt is None else max(qt.stride(0), n), _ptr(var),
+                             _ptr(Wt), 0 if Wt is None else Wt.stride(0), round_up(m + dy, 16) * round_up(m, 16), _ptr(value))
+    _native.check(st, "gpn_kfold_terms")
+    return qt, var, Wt, value
+
+
+class KFoldState:
+    """what the k-fold closed form reads off ONE factorisation f of Kyy with (L^-1 r)^T in its extra rows and a FoldTable: Kinv
+    (lower triangle of P = Kyy^-1 = U U^T, formed exactly as LooState forms it), at = a^T, the k fold blocks P[I_f, I_f] gathered
+    into equal-shape factor buffers and factorised in lock step WITHOUT jitter, qt = (y - mu)^T and var = diag Sigma_f in data
+    order, value = L_kfold and, with want_w, Wt = W_f^T and wt = w^T = (P q)^T (the factor's right-solve plus a skinny contraction
+    with U, LooState's route).  bad: some fold's factorisation reported info != 0 (ONE host read for the group of folds): value is
+    NaN and so is every gradient; nothing is clamped.  The tensors are this object's own: nothing refers to the factor buffer
+    afterwards.  The number of launches depends on neither k nor n."""
+
+    def __init__(self, f, table, want_w=True):
+        from . import _backward
+        n, dy = f.n, f.e
+        if table.n != n:
+            raise ValueError("folds partition range(%d) but the data have %d rows" % (table.n, n))
+        self.n, self.dy, self.rows, self.ld, self.table = n, dy, f.rows, f.ld, table
+        U = _backward._upper_inverse(f)
+        self.Kinv = _backward._kinv_lower(f, U)
+        kpad = round_up(n, 16)
+        self.at = gemm_nt(f.A[n:], U, dy, n, kpad, tri=TRI_B_UPPER)                  # a^T = alpha^T U^T
+        fb = FactorBatch(table.k, table.m_max, dy, f.device)
+        kfold_gather(self.Kinv, self.at, n, dy, table, fb)
+        out3, Uf = kfold_factorise(fb)
+        Bt = padded_like_factor(f, dy) if want_w else None
+        qt, self.var, self.Wt, self.value = kfold_terms(table, n, dy, fb, Uf, out3=out3, info=fb.info, qt=Bt, want_w=want_w)
+        self.fold_terms = out3                                                       # [k, 3]: sum log L_f,ii, ||beta_f||^2, (unused)
+        self.wt = None
+        if want_w:
+            f.solve_right_lt(Bt, dy)                                                 # q^T L^-T = q^T U
+            self.wt = gemm_nt(Bt, U, dy, n, kpad, tri=TRI_B_UPPER)                   # w^T = (q^T U) U^T
+            qt = None                                                                # (overwritten by the solve)
+        self.qt = qt
+        self.bad = bool((fb.info != 0).any().item())                                 # the one host read of the folds' info
+
+    def scaled_columns(self):
+        """S = [P[:, I_f] W_f]_f, [round_up(n, 16), k * round_up(m_max + dy, 16)]: gpn_kfold_columns and ONE strided-batch
+        contraction; Q = P D P = S S^T"""
+        t, n = self.table, self.n
+        wp, mp = round_up(t.m_max + self.dy, 16), round_up(t.m_max, 16)
+        C = kfold_columns(self.Kinv, n, t)
+        S = torch.empty(round_up(n, 16), t.k * wp, dtype=torch.float64, device=C.device)
+        st = _native.lib().gpn_gemm_nt_batched(_stream(C.device), n, wp, mp, 1.0, _ptr(C), mp, C.stride(0), _ptr(self.Wt), mp, wp * mp,
+                                               0.0, _ptr(S), S.stride(0), wp, 0, 0, t.k)
+        _native.check(st, "gpn_gemm_nt_batched")
+        return S
+
+
+def _nan_like(t):
+    return torch.full_like(t, float("nan"))
+
+
+class GPRKFoldLik(torch.autograd.Function):
+    """The k-fold log predictive density L_kfold = sum_f log p(y_I | y_-I, X, theta) of the exact GP in closed form from the diagonal
+    blocks of P = Kyy^-1, as one autograd node with GPRLooLik's inputs plus the FoldTable; output shape (1,).
+    Forward: the factorisation of GPRLogLik (kernel_factor: the same jitter ladder, the model's reusable factor buffer), then
+    KFoldState.  The node keeps P, a^T, w^T, W^T PRIVATELY: its backward never reads the shared factor buffer.  P_f gets no jitter:
+    a fold whose factorisation reports info != 0 makes the value and every gradient NaN.
+    Backward: gpn_kfold_columns, S = [P[:, I_f] W_f] (one strided-batch contraction), Q = S S^T (one lower contraction), the sweep
+    gpn_loo_grad; dL/dR = -w.
+    Memory, in N x N: forward peak 4 (factor, U, the inversion's workspace, P; the folds' buffers add about 3 / k); backward:
+    factor, P, the column buffer (k round_up(m_max, 16) / n: about 1 for near-equal folds, at most 4 by FoldTable's rule) and S
+    (about 1) during the block product, then -- the column buffer released -- factor, P, S, Q: a peak of about 4 for near-equal
+    folds, plus W^T (1 / k)."""
+
+    @staticmethod
+    def forward(ctx, X, R, variance, length_scales, noise, kind, holder, table):
+        n = R.shape[0]
+        if X.shape[0] != n:
+            raise ValueError("X and Y must have same # data.")
+        f = kernel_factor(kind, X, variance, length_scales, noise, R=R, factor=holder.get("factor"))
+        holder["factor"] = f
+        ctx.kind = kind
+        ctx.state = KFoldState(f, table)
+        ctx.save_for_backward(X, R, variance, length_scales, noise)
+        return ctx.state.value.reshape(1)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        X, R, variance, length_scales, noise = ctx.saved_tensors
+        s = ctx.state
+        if s.bad:
+            # a fold block was not positive definite: the value is NaN and so is every gradient
+            return (None, _nan_like(R) if ctx.needs_input_grad[1] else None, _nan_like(variance), _nan_like(length_scales), _nan_like(noise),
+                    None, None, None)
+        n = s.n
+        S = s.scaled_columns()
+        Q = torch.empty(round_up(max(n, 1), 64), s.ld, dtype=torch.float64, device=S.device)
+        gemm_nt(S, S, n, n, S.shape[1], C=Q, lower=True)                             # Q = P D P, lower triangle
+        del S
+        out = loo_grad(ctx.kind, X, variance, length_scales, Q, s.at, s.wt)
+        nls = length_scales.numel()
+        go = grad_out.reshape(())
+        return (None, -go * s.wt.t() if ctx.needs_input_grad[1] else None, go * out[0:1], go * out[1:1 + nls].reshape(length_scales.shape),
+                go * out[1 + nls:2 + nls], None, None, None)
+
+
+class DenseKFoldLik(torch.autograd.Function):
+    """GPRKFoldLik for a kernel matrix that arrives as a dense tensor (Sum / Product / Linear / White ... kernels), as DenseLooLik
+    serves the leave-one-out objective: the same native steps, Q = S S^T as a full contraction, and dL_kfold/dK = G goes back to
+    autograd as a dense [n, n] gradient (-w for R, tr G for the noise).  Memory: GPRKFoldLik's plus the dense K and G."""
+
+    @staticmethod
+    def forward(ctx, K, R, noise, table):
+        Kyy = K.detach().clone()
+        Kyy.diagonal().add_(noise.detach()[0])
+        ctx.state = KFoldState(cholesky_factor(Kyy, rhs=R), table)
+        ctx.save_for_backward(K, R, noise)
+        return ctx.state.value.reshape(1)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        K, R, noise = ctx.saved_tensors
+        s = ctx.state
+        if s.bad:
+            return (_nan_like(K) if ctx.needs_input_grad[0] else None, _nan_like(R) if ctx.needs_input_grad[1] else None,
+                    _nan_like(noise) if ctx.needs_input_grad[2] else None, None)
+        n, dy = s.n, s.dy
+        S = s.scaled_columns()
+        G = gemm_nt(S, S, n, n, S.shape[1])                                          # Q, both triangles
+        del S
+        left = torch.zeros(round_up(n, 16), round_up(2 * dy, 16), dtype=torch.float64, device=G.device)
+        right = torch.zeros_like(left)
+        left[:n, :dy], left[:n, dy:2 * dy] = s.at.t(), s.wt.t()
+        right[:n, :dy], right[:n, dy:2 * dy] = s.wt.t(), s.at.t()
+        gemm_nt(left, right, n, n, round_up(2 * dy, 16), alpha=0.5, beta=-1.0, C=G)  # G = 1/2 (a w^T + w a^T) - Q
+        go = grad_out.reshape(())
+        return (go * G if ctx.needs_input_grad[0] else None,
+                -go * s.wt.t() if ctx.needs_input_grad[1] else None,
+                (go * G.diagonal().sum()).reshape(1) if ctx.needs_input_grad[2] else None, None)
+
+
 LOG_2PI = math.log(2.0 * math.pi)

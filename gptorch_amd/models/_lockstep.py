@@ -146,6 +146,8 @@ def _lockstep_groups(models, for_grad=False):
         k = m._stationary()
         if k is None or not m.X.is_cuda or m.X.shape[0] == 0:
             continue
+        if m.objective == "kfold":                                       # k-fold models run one by one, whatever is asked of them
+            continue
         if for_grad and (_has_priors([m]) or m.objective != "lml"):      # (another objective: loss() is formed by the model itself)
             continue
         groups.setdefault(_group_key(m), []).append(i)
@@ -212,7 +214,7 @@ def _expression_groups(models):
     for i, m in enumerate(models):
         if not isinstance(m, GPR) or type(m).log_likelihood is not GPR.log_likelihood or m._stationary() is not None:
             continue
-        if not m.X.is_cuda or m.X.shape[0] == 0:
+        if not m.X.is_cuda or m.X.shape[0] == 0 or m.objective == "kfold":   # (k-fold models run one by one)
             continue
         prog = m._expression(m.X)
         if prog is None:

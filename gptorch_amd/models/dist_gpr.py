@@ -82,6 +82,8 @@ class DistGPR(GPR):
                  objective="lml"):
         if objective == "loo":
             raise NotImplementedError("DistGPR fits the log marginal likelihood only: the leave-one-out objective needs the explicit inverse on one GPU")
+        if objective == "kfold":
+            raise NotImplementedError("DistGPR fits the log marginal likelihood only: the k-fold objective needs the explicit inverse on one GPU")
         super().__init__(x, y, kernel, mean_function=mean_function, likelihood=likelihood, name=name, objective=objective)
         self._prog = None
         if not (isinstance(kernel, kernels.Stationary) and kernel._kind is not None):

@@ -18,13 +18,24 @@ BLOCKED_AFTER_CALLS = 1      # ... and before the 1024 x 1024 diagonal blocks ar
 
 
 class GPR(GPModel):
-    def __init__(self, x, y, kernel, mean_function=None, likelihood=None, name="gpr", objective="lml"):
-        """objective: what loss() / optimize() fit -- "lml", the log marginal likelihood (the reference's only objective), or "loo",
-        the leave-one-out log predictive density (loo_log_predictive).  log_likelihood() is the LML either way."""
+    def __init__(self, x, y, kernel, mean_function=None, likelihood=None, name="gpr", objective="lml", folds=None):
+        """objective: what loss() / optimize() fit -- "lml", the log marginal likelihood (the reference's only objective), "loo",
+        the leave-one-out log predictive density (loo_log_predictive), or "kfold", the k-fold log predictive density in closed form
+        (kfold_log_predictive).  log_likelihood() is the LML in every case.
+        folds (objective="kfold" only; required there): an int k >= 2 -- np.array_split(np.arange(n), k): CONTIGUOUS blocks in data
+        order, no shuffling (shuffle the data, or pass index arrays, when the order carries structure) -- or a sequence of integer
+        index arrays that partition range(n): every index exactly once, no empty fold, at least two folds (ValueError otherwise).
+        Folds are padded to the largest: a partition with k * round_up(m_max, 16) > 4 round_up(n, 16) raises NotImplementedError (all-singleton
+        folds among them: that is objective="loo")."""
         super().__init__(x, y, kernel, likelihood, mean_function, name)
-        if objective not in ("lml", "loo"):
-            raise ValueError("objective must be 'lml' or 'loo'; got %r" % (objective,))
+        if objective not in ("lml", "loo", "kfold"):
+            raise ValueError("objective must be 'lml', 'loo' or 'kfold'; got %r" % (objective,))
         self.objective = objective
+        self.folds = None
+        if objective == "kfold":
+            self.folds = _ops.FoldTable(folds, self.X.shape[0])
+        elif folds is not None:
+            raise ValueError("folds belongs to objective='kfold'; got objective=%r" % (objective,))
         self._holder = {}        # reusable factor buffer for the training loop
         self._predict_cache = None
         self._predict_calls = 0
@@ -96,10 +107,58 @@ class GPR(GPModel):
             s = _ops.LooState(f, want_w=False)
             return y - s.qt.t(), s.var[:, None].expand(y.shape[0], y.shape[1]).clone()
 
+    def _fold_table(self, n, folds):
+        if folds is None:
+            folds = self.folds
+        if not isinstance(folds, _ops.FoldTable):
+            folds = _ops.FoldTable(folds, n)
+        if folds.n != n:
+            raise ValueError("folds partition range(%d) but the data have %d rows" % (folds.n, n))
+        return folds
+
+    def kfold_log_predictive(self, x=None, y=None, folds=None):
+        """sum_f log p(y_I | X, y_-I, theta) over the folds (default: the constructor's), the k-fold log predictive density in closed
+        form from ONE factorisation and the diagonal blocks of Kyy^-1; differentiable w.r.t. kernel parameters, noise and mean
+        function, shape (1,).  Kernels without a native kind (composites included) hand their dense K(x) to the same native steps."""
+        x = x if x is not None else self.X
+        y = y if y is not None else self.Y
+        if not x.shape[0] == y.shape[0]:
+            raise ValueError("X and Y must have same # data.")
+        table = self._fold_table(x.shape[0], folds)
+        k = self._stationary()
+        resid = y - self.mean_function(x)
+        if k is None:
+            return _ops.DenseKFoldLik.apply(self.kernel.K(x), resid, self.likelihood.variance.transform(), table)
+        return _ops.GPRKFoldLik.apply(x, resid, k.variance.transform(), k.length_scales.transform(),
+                                      self.likelihood.variance.transform(), k._kind, self._holder, table)
+
+    def kfold_predict(self, x=None, y=None, folds=None):
+        """(mean [n, dy], var [n, dy]) in DATA order: for each point the marginal predictive of the OBSERVATION (noise included) from
+        the model that never saw the point's fold -- what kfold_log_predictive scores, without the covariances inside a fold; from
+        one factorisation; no gradients."""
+        self._auto_place()
+        x = x if x is not None else self.X
+        y = y if y is not None else self.Y
+        if not x.shape[0] == y.shape[0]:
+            raise ValueError("X and Y must have same # data.")
+        table = self._fold_table(x.shape[0], folds)
+        with torch.no_grad():
+            k = self._stationary()
+            resid = y - self.mean_function(x)
+            noise = self.likelihood.variance.transform()
+            if k is None:
+                f = _ops.cholesky_factor(self._compute_kyy(x), rhs=resid)
+            else:
+                f = _ops.kernel_factor(k._kind, x, k.variance.transform(), k.length_scales.transform(), noise, R=resid)
+            s = _ops.KFoldState(f, table, want_w=False)
+            return y - s.qt.t(), s.var[:, None].expand(y.shape[0], y.shape[1]).clone()
+
     def _loss(self, *args, **kwargs):
         if self.objective == "lml":
             return super()._loss(*args, **kwargs)
         self._auto_place()
+        if self.objective == "kfold":
+            return -(self.kfold_log_predictive(*args, **kwargs) + self.log_prior())
         return -(self.loo_log_predictive(*args, **kwargs) + self.log_prior())
 
     def _compute_kyy(self, x=None):

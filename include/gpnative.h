@@ -904,6 +904,45 @@ int gpn_loo_grad_batched(void* stream, int kind, int batch, const double* X, int
                          int64_t ldat, int64_t sAt, const double* wt, int64_t ldwt, int64_t sWt, int dy, double* work,
                          int64_t work_bytes, double* out);
 
+/* ---- k-fold cross-validation of the exact GP in closed form (GPR(objective="kfold"); csrc/kfold.hip) ------------------------
+ * With P = Kyy^-1 (lower triangle), a = P r and a partition of the n points into k folds -- fold f: the m_f indices
+ * fold_idx[fold_off[f] .. fold_off[f + 1]) (DEVICE int32 tables, fold_off [k + 1]; any order, need not be sorted or contiguous;
+ * m_max >= every m_f) -- and P_f = P[I_f, I_f] = L_f L_f^T, U_f = L_f^-T, beta_f = L_f^-1 a_I:
+ *   y_I - mu_I = q_I = U_f beta_f,  held-out covariance of the observations Sigma_f = U_f U_f^T,
+ *   L_kfold = sum_f (dy sum_i log L_f,ii - 1/2 ||beta_f||^2) - 1/2 n dy log 2 pi,
+ *   Q = P blockdiag_f(1/2 (dy Sigma_f + q_I q_I^T)) P = S S^T,  S = [P[:, I_f] W_f]_f,  W_f = [sqrt(dy/2) U_f | sqrt(1/2) q_I],
+ *   dL_kfold/dtheta = sum_ij G_ij dKyy_ij/dtheta with G = -Q + 1/2 (a w^T + w a^T), w = P q: gpn_loo_grad's sweep, unchanged.
+ * The folds run as k equal-shape problems through gpn_potrf_lower_batched / gpn_lml_reduce_batched / gpn_trtri_upper_batched /
+ * gpn_gemm_nt_batched.  Every entry validates its arguments before any launch (-k: the k-th argument, the stream being the
+ * first; more than 65535 folds -- a grid dimension --: GPN_E_UNSUPPORTED), issues a number of launches that depends on neither k
+ * nor n, adds up in a fixed order without atomics (the same call twice gives the same bits) and synchronises nothing.  A table entry
+ * outside [0, n), or the part of a fold beyond m_max, is never followed: it reads nothing and writes nothing. */
+/* Fold gather, a pure copy: into the ZEROED factor buffers A + f*sA (gpn_factor_rows(m_max, dy) rows, lda >= gpn_factor_ld(m_max,
+ * dy)) of fold f -- entry (i, j), i, j < m_f, = P[max(I_i, I_j), min(I_i, I_j)] read from the lower triangle of Kinv (any ldk >= n);
+ * the padding i or j in [m_f, m_max): 1 on the diagonal, 0 elsewhere (the padded problem is exact: log 1 = 0, the padding is
+ * decoupled); extra row m_max + c, c < dy: a_I^T from at = a^T [dy, n] (ldat), 0 on the padding.  Nothing outside rows
+ * [0, m_max + dy) x columns [0, m_max) of a buffer is written. */
+int gpn_kfold_gather(void* stream, int64_t n, int dy, const double* Kinv, int64_t ldk, const double* at, int64_t ldat,
+                     int k, const int32_t* fold_off, const int32_t* fold_idx, int64_t m_max, double* A, int64_t lda, int64_t sA);
+/* Column gather: C + f*sC, [round_up(n, 16), ldc] (ldc >= round_up(m_max, 16); ldc, sC even, C 16-byte aligned: an A operand of
+ * gpn_gemm_nt_batched) <- P[:, I_f], column j < m_f = the FULL column I_j of the symmetric P (rows above the diagonal from the
+ * mirror, read along the rows of Kinv through LDS); every other entry of [round_up(n, 16), round_up(m_max, 16)] <- 0 (C need not be
+ * zeroed) and nothing outside it is written.  gpn_kfold_columns_work_bytes(n, k, m_max): the bytes of the packed buffer. */
+int64_t gpn_kfold_columns_work_bytes(int64_t n, int k, int64_t m_max);
+int gpn_kfold_columns(void* stream, int64_t n, const double* Kinv, int64_t ldk, int k, const int32_t* fold_off,
+                      const int32_t* fold_idx, int64_t m_max, double* C, int64_t ldc, int64_t sC);
+/* Weights, terms, value, from U_f = U + f*sU (ldu; gpn_trtri_upper_batched of the factorised fold buffers) and beta_f^T = the extra
+ * rows of A + f*sA: qt [dy, n] (ldqt) = q^T and var [n] = diag Sigma_f (row sums of squares of U_f), both in DATA order;
+ * Wt + f*sW ([round_up(m_max + dy, 16), ldw], ldw >= round_up(m_max, 16), ZEROED by the caller) = W_f^T, the B operand of
+ * S_f = P[:, I_f] W_f: rows j < m_f = sqrt(dy/2) U_f^T, rows m_max + c = sqrt(1/2) q_I^T;
+ * value[0] = L_kfold from out3 [k, 3] of gpn_lml_reduce_batched over the fold buffers, summed by one workgroup, NaN when any
+ * info[f] != 0 (info may be NULL; nothing is clamped, P_f gets no jitter).  qt, var, Wt, value may each be NULL.
+ * gpn_kfold_weights_work_bytes(k, m_max, dy): the bytes of the packed W^T buffer. */
+int64_t gpn_kfold_weights_work_bytes(int k, int64_t m_max, int dy);
+int gpn_kfold_terms(void* stream, int64_t n, int dy, int k, const int32_t* fold_off, const int32_t* fold_idx, int64_t m_max,
+                    const double* U, int64_t ldu, int64_t sU, const double* A, int64_t lda, int64_t sA, const double* out3,
+                    const int32_t* info, double* qt, int64_t ldqt, double* var, double* Wt, int64_t ldw, int64_t sW, double* value);
+
 /* ---- optional launch profiler (bench.py's roofline legs) ---------------------- */
 /* While enabled, every contraction / assembly / gradient-sweep / leaf launch of this library is bracketed by two HIP events
  * recorded ON THE LAUNCH STREAM (what SURVEY 8(d) asks the SYRK fraction to be measured with).  Off by default; the
