@@ -17,6 +17,7 @@ from gptorch_amd import kernels, likelihoods, mean_functions, rng
 from gptorch_amd.models import GPR, VFE
 from oracle import gp_oracle as orc
 from tests import _xref as xr
+from tests._refine_ref import points as _points        # the planted rows (shared with the refinement's tests)
 
 pytestmark = pytest.mark.gpu
 
@@ -31,22 +32,6 @@ def _t(a, device=None, grad=False):
 
 def _ls(d, ard, seed, scale):
     return scale * (0.6 + 0.8 * rng.uniform(seed, d)) if ard else float(scale)
-
-
-def _points(seed, n, d, ls0, first=0):
-    """n random rows with the edges of the kernels planted (from row `first` on, spread over the tiles): exactly repeated
-    rows, rows 1e-21 ell apart (r^2 = 1e-42, under the clamp), 1e-19 ell apart (r^2 = 1e-38, just above it), a row 1000 ell
-    away (every exp underflows) and rows at r = pi/2 +- 1e-3, pi +- 1e-3 from the origin (Periodic's sign changes)."""
-    x = rng.normal(seed, (n, d))
-    e0 = np.zeros(d)
-    e0[0] = ls0
-    special = [np.zeros(d), 1e-21 * e0, 1e-19 * e0, None, 1000.0 * e0,
-               (math.pi / 2 - 1e-3) * e0, (math.pi / 2 + 1e-3) * e0, (math.pi - 1e-3) * e0, (math.pi + 1e-3) * e0, np.zeros(d)]
-    rows = [first + 7 * i for i in range(len(special))]
-    for r, s in zip(rows, special):
-        if r < n:
-            x[r] = x[rows[0] + 1 if rows[0] + 1 < n else 0] if s is None else s
-    return x
 
 
 def _direct64(kind, xn, x2n, ls, wn):
