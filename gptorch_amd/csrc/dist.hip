@@ -408,7 +408,7 @@ static int dist_evaluate(void* stream, const gpn_dist_comm* comm, int rank, int 
   if (rc != GPN_OK) return rc;
   if (ns > 0 && (with_grad || !Xs || !pmean || !pvar)) return -20;
   if (pr * pc > 1 && (!comm || !comm->bcast || !comm->allreduce)) return -2;
-  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -6;
+  if (!kind_is_covariance(kind)) return -6;
   if (!X) return -7;
   if (n <= 0) return -8;
   if (d <= 0) return -9;
@@ -795,7 +795,7 @@ extern "C" int gpn_dist_lml_refine(void* stream, const gpn_dist_comm* comm, int 
   int rc = make_geom(g, rank, pr, pc, n, dy, tile);
   if (rc != GPN_OK) return rc;
   if (pr * pc > 1 && (!comm || !comm->allreduce)) return -2;
-  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -6;
+  if (!kind_is_covariance(kind)) return -6;
   if (!X) return -7;
   if (n <= 0) return -8;
   if (d <= 0) return -9;

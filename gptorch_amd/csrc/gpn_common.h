@@ -23,6 +23,10 @@ constexpr int LEAF = 128;  // diagonal leaf block (potrf + inverse in one workgr
 
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
+// the kinds that are covariance functions (Rbf .. Exp, Periodic): what every entry point that factors, solves against or
+// multiplies by K takes.  GPN_SQDIST (K = r^2, no covariance) is served by the assembly and the gradient sweeps only.
+inline bool kind_is_covariance(int kind) { return (kind >= GPN_RBF && kind <= GPN_EXP) || kind == GPN_PERIODIC; }
+
 void set_hip_error(hipError_t e, const char* where);
 
 #define GPN_HIP_CHECK(expr)                          \

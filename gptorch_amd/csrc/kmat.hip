@@ -221,7 +221,7 @@ int pack_rhs_full(hipStream_t s, const double* Y, const double* M, int64_t n, in
 // K(X) + noise I, lower tiles, into A AND into Ksave (same leading dimension): gpn_lml_forward_saving
 int assemble_lower_saving(hipStream_t s, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
                           int nls, const double* noise, double* A, double* Ksave, int64_t lda) {
-  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;
+  if (!kind_is_covariance(kind)) return -2;
   KmatArgs a;
   a.X = X; a.X2 = X;
   a.variance = variance; a.ls = length_scales; a.noise = noise;
@@ -239,7 +239,8 @@ int assemble_lower_saving(hipStream_t s, int kind, const double* X, int64_t n, i
     case GPN_MATERN52: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, a); break;
     case GPN_MATERN32: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, a); break;
     case GPN_EXP: hipLaunchKernelGGL(kmat_kernel<GPN_EXP>, grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL(kmat_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, a); break;
+    case GPN_PERIODIC: hipLaunchKernelGGL(kmat_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, a); break;
+    default: return -2;
   }
   if (rec >= 0) profile_end(s, rec);
   GPN_LAUNCH_CHECK();
@@ -249,6 +250,7 @@ int assemble_lower_saving(hipStream_t s, int kind, const double* X, int64_t n, i
 // B = I + diag(sc) K(X) diag(sc), entries on and below the diagonal, into A (laplace.hip; gpn_laplace_system)
 int assemble_laplace_system(hipStream_t s, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
                             int nls, const double* sc, double* A, int64_t lda) {
+  if (!kind_is_covariance(kind)) return -2;       // (before the profile record opens: the switch below cannot leave it open)
   KmatArgs a;
   a.X = X; a.X2 = X;
   a.variance = variance; a.ls = length_scales; a.noise = nullptr; a.sc = sc;
@@ -278,6 +280,7 @@ int assemble_laplace_system(hipStream_t s, int kind, const double* X, int64_t n,
 int assemble_laplace_system_batched(hipStream_t s, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                                     const double* variance, const double* length_scales, int nls, const double* sc, int64_t sSc,
                                     double* A, int64_t lda, int64_t sA) {
+  if (!kind_is_covariance(kind)) return -2;       // (before the profile record opens: the switch below cannot leave it open)
   KmatArgs a;
   a.X = X; a.X2 = X;
   a.variance = variance; a.ls = length_scales; a.noise = nullptr; a.sc = sc; a.sSc = sSc;
@@ -307,6 +310,7 @@ int assemble_laplace_system_batched(hipStream_t s, int kind, int batch, const do
 int assemble_batched(hipStream_t s, int kind, int batch, const double* X, int64_t sX, int64_t n, int d, const double* Y, int64_t sY,
                      const double* M, int64_t sM, int dy, const double* variance, const double* length_scales, int nls,
                      const double* noise, double* A, int64_t lda, int64_t sA, int32_t* info, const int32_t* n_of) {
+  if (!kind_is_covariance(kind)) return -2;       // (before the profile record opens: the switch below cannot leave it open)
   KmatArgs a;
   a.n_of = n_of;
   a.X = X; a.X2 = X;
@@ -378,7 +382,8 @@ extern "C" int gpn_kernel_matrix(void* stream, int kind, const double* X, int64_
     case GPN_MATERN32: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, a); break;
     case GPN_EXP: hipLaunchKernelGGL(kmat_kernel<GPN_EXP>, grid, dim3(256), 0, s, a); break;
     case GPN_PERIODIC: hipLaunchKernelGGL(kmat_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL(kmat_kernel<GPN_SQDIST>, grid, dim3(256), 0, s, a); break;
+    case GPN_SQDIST: hipLaunchKernelGGL(kmat_kernel<GPN_SQDIST>, grid, dim3(256), 0, s, a); break;
+    default: return -2;
   }
   if (rec >= 0) profile_end(s, rec);
   GPN_LAUNCH_CHECK();
@@ -431,7 +436,9 @@ extern "C" int gpn_kernel_matrix_batched(void* stream, int kind, int batch, cons
     case GPN_MATERN52: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, a); break;
     case GPN_MATERN32: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, a); break;
     case GPN_EXP: hipLaunchKernelGGL(kmat_kernel<GPN_EXP>, grid, dim3(256), 0, s, a); break;
-    default: hipLaunchKernelGGL(kmat_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, a); break;
+    case GPN_PERIODIC: hipLaunchKernelGGL(kmat_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, a); break;
+    case GPN_SQDIST: hipLaunchKernelGGL(kmat_kernel<GPN_SQDIST>, grid, dim3(256), 0, s, a); break;
+    default: return -2;
   }
   if (rec >= 0) profile_end(s, rec);
   GPN_LAUNCH_CHECK();

@@ -453,7 +453,7 @@ constexpr int LAP_MAX_BATCH = 65535;      // the model index is a grid's y (z) d
 static int lap_check(bool lockstep, int kind, int batch, const double* X, int64_t sX, int64_t n, int d, const double* variance,
                      const double* length_scales, int nls) {
   const int at_X = lockstep ? 4 : 3, at_n = lockstep ? 6 : 4;
-  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;
+  if (!kind_is_covariance(kind)) return -2;
   if (batch < 1) return -3;
   if (!X) return -at_X;
   if (sX < 0) return -5;
@@ -494,6 +494,7 @@ static int lik_derivs_launch(hipStream_t s, int kind, int batch, const double* f
 // the tile sweep of `batch` models and the gather of their rows (n > 0)
 template <int MODE>
 static int lap_rows_launch(hipStream_t s, int kind, int batch, const LapArgs& p, const LapStrides& st, const double* divide, double* out) {
+  if (!kind_is_covariance(kind)) return -2;
   const int64_t t = p.tiles;
   if (t * (t + 1) / 2 > 0x7fffffff || batch > LAP_MAX_BATCH) return GPN_E_UNSUPPORTED;
   const dim3 grid((unsigned)(t * (t + 1) / 2), (unsigned)batch);
@@ -502,7 +503,8 @@ static int lap_rows_launch(hipStream_t s, int kind, int batch, const LapArgs& p,
     case GPN_MATERN52: hipLaunchKernelGGL((lap_rows_kernel<GPN_MATERN52, MODE>), grid, dim3(256), 0, s, p, st); break;
     case GPN_MATERN32: hipLaunchKernelGGL((lap_rows_kernel<GPN_MATERN32, MODE>), grid, dim3(256), 0, s, p, st); break;
     case GPN_EXP: hipLaunchKernelGGL((lap_rows_kernel<GPN_EXP, MODE>), grid, dim3(256), 0, s, p, st); break;
-    default: hipLaunchKernelGGL((lap_rows_kernel<GPN_PERIODIC, MODE>), grid, dim3(256), 0, s, p, st); break;
+    case GPN_PERIODIC: hipLaunchKernelGGL((lap_rows_kernel<GPN_PERIODIC, MODE>), grid, dim3(256), 0, s, p, st); break;
+    default: return -2;
   }
   GPN_LAUNCH_CHECK();
   hipLaunchKernelGGL(lap_gather_kernel, dim3((unsigned)((p.n + 255) / 256), (unsigned)batch), dim3(256), 0, s, p.work, p.tiles, (int64_t)p.n,
@@ -514,6 +516,7 @@ static int lap_rows_launch(hipStream_t s, int kind, int batch, const LapArgs& p,
 // the gradient sweep of `batch` models (p.a, p.u, p.d1 set; model b's partials st.work after model 0's) and its reduce into
 // out [batch, 1 + nls]
 static int lap_grad_launch(hipStream_t s, int kind, int batch, LapArgs p, const LapStrides& st, double* out) {
+  if (!kind_is_covariance(kind)) return -2;       // (before the profile record opens)
   p.nout = 1 + p.nls;
   if (p.n == 0) {
     GPN_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)batch * p.nout * sizeof(double), s));
@@ -530,7 +533,8 @@ static int lap_grad_launch(hipStream_t s, int kind, int batch, LapArgs p, const 
     case GPN_MATERN52: hipLaunchKernelGGL(lap_grad_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, p, st); break;
     case GPN_MATERN32: hipLaunchKernelGGL(lap_grad_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, p, st); break;
     case GPN_EXP: hipLaunchKernelGGL(lap_grad_kernel<GPN_EXP>, grid, dim3(256), 0, s, p, st); break;
-    default: hipLaunchKernelGGL(lap_grad_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, p, st); break;
+    case GPN_PERIODIC: hipLaunchKernelGGL(lap_grad_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, p, st); break;
+    default: return -2;
   }
   if (rec >= 0) profile_end(s, rec);
   GPN_LAUNCH_CHECK();

@@ -436,6 +436,7 @@ static int loo_scale_launch(hipStream_t s, int batch, int64_t n, const double* K
 
 // p: model 0's operands; work holds batch x tiles x nout partials, out [batch, nout]
 static int loo_grad_launch(hipStream_t s, int kind, int batch, LooGradArgs p, const LooGradStrides& st, double* out) {
+  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;      // (every kind has a case below; before the profile record opens)
   const int64_t n = p.n, t = loo_tiles(n), nblocks = t * (t + 1) / 2;
   if (nblocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
   const double nn = (double)n;
@@ -453,7 +454,8 @@ static int loo_grad_launch(hipStream_t s, int kind, int batch, LooGradArgs p, co
       case GPN_MATERN32: hipLaunchKernelGGL(loo_grad_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, q, st); break;
       case GPN_EXP: hipLaunchKernelGGL(loo_grad_kernel<GPN_EXP>, grid, dim3(256), 0, s, q, st); break;
       case GPN_SQDIST: hipLaunchKernelGGL(loo_grad_kernel<GPN_SQDIST>, grid, dim3(256), 0, s, q, st); break;
-      default: hipLaunchKernelGGL(loo_grad_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, q, st); break;
+      case GPN_PERIODIC: hipLaunchKernelGGL(loo_grad_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, q, st); break;
+      default: return -2;
     }
     if (rec >= 0) profile_end(s, rec);
     GPN_LAUNCH_CHECK();

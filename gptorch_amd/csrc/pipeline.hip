@@ -101,6 +101,7 @@ extern "C" int gpn_lml_forward(void* stream, int kind, const double* X, int64_t 
                                const double* variance, const double* length_scales, int nls,
                                const double* noise, double* A, int64_t lda, double* winv,
                                int32_t* info, double* out3) {
+  if (!kind_is_covariance(kind)) return -2;
   if (n < 0) return -4;
   if (!Y) return -6;
   if (dy <= 0) return -8;
@@ -133,6 +134,7 @@ extern "C" int gpn_lml_forward_saving(void* stream, int kind, const double* X, i
                                       const double* variance, const double* length_scales, int nls,
                                       const double* noise, double* A, int64_t lda, double* winv,
                                       int32_t* info, double* out3, double* Ksave) {
+  if (!kind_is_covariance(kind)) return -2;
   if (!X) return -3;
   if (n <= 0) return -4;
   if (d <= 0) return -5;
@@ -166,7 +168,7 @@ extern "C" int gpn_lml_forward_batched(void* stream, int kind, int batch, const 
                                        const double* Y, int64_t sY, const double* M, int64_t sM, int dy,
                                        const double* variance, const double* length_scales, int nls, const double* noise,
                                        double* A, int64_t lda, int64_t sA, double* winv, int64_t sW, int32_t* info, double* out3) {
-  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;
+  if (!kind_is_covariance(kind)) return -2;
   if (batch < 1) return -3;
   if (!X) return -4;
   if (n < 0) return -6;
@@ -207,7 +209,7 @@ extern "C" int gpn_lml_forward_ragged(void* stream, int kind, int batch, const d
                                       const double* Y, int64_t sY, int dy,
                                       const double* variance, const double* length_scales, int nls, const double* noise,
                                       double* A, int64_t lda, int64_t sA, double* winv, int64_t sW, int32_t* info, double* out3) {
-  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;
+  if (!kind_is_covariance(kind)) return -2;
   if (batch < 1) return -3;
   if (!X) return -4;
   if (n <= 2 * 128) return -6;
@@ -243,6 +245,7 @@ extern "C" int gpn_lml_backward(void* stream, int kind, const double* X, int64_t
                                 const double* variance, const double* length_scales, int nls,
                                 const double* A, int64_t lda, const double* winv, int dy,
                                 double* work, double* grads, double* grad_resid) {
+  if (!kind_is_covariance(kind)) return -2;
   if (n < 0) return -4;
   if (!A) return -9;
   if (dy <= 0) return -12;
@@ -376,7 +379,7 @@ extern "C" int gpn_lml_backward_batched(void* stream, int kind, int batch, const
                                         const double* variance, const double* length_scales, int nls,
                                         const double* A, int64_t lda, int64_t sA, const double* winv, int64_t sW, int dy,
                                         double* work, double* grads, double* grad_resid) {
-  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;
+  if (!kind_is_covariance(kind)) return -2;
   if (batch < 1) return -3;
   if (!X) return -4;
   if (n < 0) return -6;
@@ -443,7 +446,7 @@ extern "C" int gpn_lml_backward_ragged(void* stream, int kind, int batch, const 
                                        const double* variance, const double* length_scales, int nls,
                                        const double* A, int64_t lda, int64_t sA, const double* winv, int64_t sW, int dy,
                                        double* work, double* grads) {
-  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;
+  if (!kind_is_covariance(kind)) return -2;
   if (batch < 1) return -3;
   if (!X) return -4;
   if (n <= 2 * 128) return -6;
@@ -487,6 +490,7 @@ static int predict_impl(void* stream, int kind, const double* X, int64_t n, int 
                         const double* variance, const double* length_scales, int nls,
                         const double* A, int64_t lda, const double* winv, const double* wb, int dy, int full_cov,
                         double* work, double* mean, double* var) {
+  if (!kind_is_covariance(kind)) return -2;
   if (n < 0) return -4;
   if (!Xs) return -6;
   if (ns < 0) return -7;

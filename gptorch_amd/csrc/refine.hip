@@ -619,7 +619,7 @@ extern "C" int gpn_lml_refine(void* stream, int kind, const double* X, int64_t n
                               const double* Y, const double* M, int dy,
                               const double* variance, const double* length_scales, int nls, const double* noise,
                               const double* A, int64_t lda, const double* winv, double* work, double* out3) {
-  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;
+  if (!kind_is_covariance(kind)) return -2;
   if (!X) return -3;
   if (n < 0) return -4;
   if (d <= 0) return -5;
@@ -654,7 +654,8 @@ extern "C" int gpn_lml_refine(void* stream, int kind, const double* X, int64_t n
     case GPN_MATERN52: GPN_RESID(GPN_MATERN52); break;
     case GPN_MATERN32: GPN_RESID(GPN_MATERN32); break;
     case GPN_EXP: GPN_RESID(GPN_EXP); break;
-    default: GPN_RESID(GPN_PERIODIC); break;
+    case GPN_PERIODIC: GPN_RESID(GPN_PERIODIC); break;
+    default: return -2;
   }
 #undef GPN_RESID
   GPN_LAUNCH_CHECK();
@@ -772,7 +773,7 @@ extern "C" int64_t gpn_refine_tile_count(int64_t n) {
 extern "C" int gpn_refine_resid_part(void* stream, int kind, const double* X, int64_t n, int d,
                                      const double* variance, const double* length_scales, int nls, const double* noise,
                                      const double* a, int dy, int64_t q0, int64_t q1, double* work, double* ka) {
-  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;
+  if (!kind_is_covariance(kind)) return -2;
   if (!X) return -3;
   if (n <= 0) return -4;
   if (d <= 0) return -5;
@@ -804,7 +805,8 @@ extern "C" int gpn_refine_resid_part(void* stream, int kind, const double* X, in
       case GPN_MATERN52: GPN_RESID(GPN_MATERN52); break;
       case GPN_MATERN32: GPN_RESID(GPN_MATERN32); break;
       case GPN_EXP: GPN_RESID(GPN_EXP); break;
-      default: GPN_RESID(GPN_PERIODIC); break;
+      case GPN_PERIODIC: GPN_RESID(GPN_PERIODIC); break;
+      default: return -2;
     }
 #undef GPN_RESID
     GPN_LAUNCH_CHECK();

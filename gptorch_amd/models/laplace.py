@@ -113,8 +113,9 @@ def find_mode(kind, lik_kind, X, y, m, var, ls, a0=None, factor=None, newton_tol
             # the step's ONE host read: psi before and after, the two maxima of the stopping rule, the factorisation's info
             got, was, max_df, max_f, info = torch.stack([psi_t, psi, (f_t - f).abs().max(), f_t.abs().max(), factor.info[0].double()]).tolist()
             if info != 0:
-                raise NativeError("LaplaceGP: the factorisation of B = I + W^1/2 K W^1/2 reported info = %d (its eigenvalues are >= 1: "
-                                  "a non-finite parameter or input?)" % int(info))
+                raise NativeError("LaplaceGP: the factorisation of B = I + W^1/2 K W^1/2 reported info = %d (for a positive "
+                                  "semi-definite K its eigenvalues are >= 1: a non-finite parameter or input -- or a kernel that "
+                                  "is not positive semi-definite, as Periodic is from two input dimensions on?)" % int(info))
             if got >= was - PSI_SLACK * (1.0 + abs(was)) or h == MAX_HALVINGS:       # (NaN / -inf: not accepted, halve)
                 break
             t *= 0.5

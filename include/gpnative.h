@@ -44,6 +44,17 @@ extern "C" {
 enum { GPN_RBF = 0, GPN_MATERN52 = 1, GPN_MATERN32 = 2, GPN_EXP = 3,
        GPN_SQDIST = 4 /* util.squared_distance itself (util.py:73-88): K = r^2, variance ignored */,
        GPN_PERIODIC = 5 /* kernels.py:228-235: variance * cos(r) */ };
+/* Which kinds an entry point with an `int kind` serves (tests/_kind_ref.py SERVED holds the same table; tests/test_gpu_kind_dispatch.py
+ * runs every entry with every kind).  Any other value -- out of range, or GPN_SQDIST where it is not listed -- is refused with the
+ * kind's argument index as a negative status (-2; the gpn_dist_* entries: -6) BEFORE anything is launched or written:
+ *   all six kinds, GPN_SQDIST included (the assembly and the gradient sweeps, which have a SqDist instantiation):
+ *     gpn_kernel_matrix(_batched), gpn_kernel_grad(_batched), gpn_kernel_grad_x2(_batched), gpn_lml_grad(_batched),
+ *     gpn_loo_grad(_batched)
+ *   the five covariance functions GPN_RBF, GPN_MATERN52, GPN_MATERN32, GPN_EXP, GPN_PERIODIC (everything that factors K, solves
+ *   against it or multiplies by it -- r^2 is no covariance):
+ *     gpn_lml_forward(_saving / _batched / _ragged), gpn_lml_backward(_batched / _ragged), gpn_lml_refine, gpn_refine_resid_part,
+ *     gpn_predict(_blocked), gpn_laplace_system / _matvec / _diag / _grad (_batched), gpn_dist_lml_forward / _grad / _refine,
+ *     gpn_dist_predict; likewise the stationary leaves of gpn_expr_term. */
 enum { GPN_FULL = 0, GPN_LOWER = 1 };
 
 enum {
@@ -76,7 +87,8 @@ int64_t gpn_winv_bytes(int64_t n);
  * variance[1], length_scales[nls] (nls = 1 or d), noise[1] or NULL: device scalars
  * in CONSTRAINED space.  uplo = GPN_LOWER (only with X2 == NULL) writes tiles on
  * or below the diagonal only.  Distances are direct differences (no Gram trick),
- * so r^2 >= 0 by construction (the clamp of util.py:88 is the identity). */
+ * so r^2 >= 0 by construction (the clamp of util.py:88 is the identity).  kind: all six (GPN_SQDIST: K = r^2). */
+/* kind: all six, GPN_SQDIST included (table at GPN_FULL above). */
 int gpn_kernel_matrix(void* stream, int kind,
                       const double* X, int64_t n, const double* X2, int64_t m, int d,
                       const double* variance, const double* length_scales, int nls,
@@ -232,7 +244,8 @@ int gpn_gemm_nt_batched_scaled(void* stream, int64_t M, int64_t N, int64_t K, co
  * sX = 0: shared points), hyper-parameters consecutive (variance[b], length_scales + b nls, noise[b]).  Each is per model
  * BIT-IDENTICAL to its single-model entry point.  They carry the sparse bound (sparse_gpr.py:108-153) of B restarts in lock
  * step -- K(Z_b), K(x, Z_b), the right-solve against chol K(Z_b), L_b^-T, the sweeps against dF/dKuu and dF/dKuf -- where the
- * reference runs one model per optimiser step (models/base.py:260-269). */
+ * reference runs one model per optimiser step (models/base.py:260-269).  kind: all six, as their single forms. */
+/* kind: all six, GPN_SQDIST included (table at GPN_FULL above). */
 int gpn_kernel_matrix_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n,
                               const double* X2, int64_t sX2, int64_t m, int d,
                               const double* variance, const double* length_scales, int nls, const double* noise,
@@ -243,11 +256,13 @@ int gpn_trsm_right_lt_batched(void* stream, const double* L, int64_t n, int64_t 
 int gpn_trtri_upper_batched(void* stream, const double* L, int64_t n, int64_t ldl, int64_t sL, const double* winv, int64_t sW,
                             double* U, int64_t ldu, int64_t sU, double* S, int64_t lds, int64_t sS, int batch);
 /* out [batch, 1 + nls]; work: batch * gpn_grad_work_bytes(n, m, nls, 0) */
+/* kind: all six, GPN_SQDIST included (table at GPN_FULL above). */
 int gpn_kernel_grad_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n,
                             const double* X2, int64_t sX2, int64_t m, int d,
                             const double* variance, const double* length_scales, int nls,
                             const double* G, int64_t ldg, int64_t sG, double* work, double* out);
 /* out [batch, m, d]; work: batch * gpn_grad_x2_work_bytes(n, m, d) */
+/* kind: all six, GPN_SQDIST included (table at GPN_FULL above). */
 int gpn_kernel_grad_x2_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n,
                                const double* X2, int64_t sX2, int64_t m, int d,
                                const double* variance, const double* length_scales, int nls,
@@ -274,7 +289,9 @@ int64_t gpn_grad_work_bytes(int64_t n, int64_t m, int nls, int lml);
 
 /* out[0] = dLML/d variance, out[1..nls] = dLML/d length_scales, out[1+nls] = dLML/d noise
  * (all w.r.t. the CONSTRAINED values) from G = 1/2 (a a^T - dy Kinv), Kinv lower [n,n],
- * at = a^T [dy, n]; K and dK/dtheta are recomputed from X on the fly (kernels.py:149-222). */
+ * at = a^T [dy, n]; K and dK/dtheta are recomputed from X on the fly (kernels.py:149-222).  kind: all six (this and the two
+ * autograd sweeps below; GPN_SQDIST has no variance: out[0] = 0). */
+/* kind: all six, GPN_SQDIST included (table at GPN_FULL above). */
 int gpn_lml_grad(void* stream, int kind, const double* X, int64_t n, int d,
                  const double* variance, const double* length_scales, int nls,
                  const double* Kinv, int64_t ldk, const double* at, int64_t ldat, int dy,
@@ -282,6 +299,7 @@ int gpn_lml_grad(void* stream, int kind, const double* X, int64_t n, int d,
 /* gpn_lml_grad for `batch` lock-step models as one sweep launch + one reduction launch: model b reads X + b*sX (0: shared),
  * variance[b], length_scales[b*nls ..], Kinv + b*sK, at + b*sAt and writes out[b*(2+nls) ..]; work: batch *
  * gpn_grad_work_bytes(n, n, nls, 1).  Bit-identical per model to gpn_lml_grad. */
+/* kind: all six, GPN_SQDIST included (table at GPN_FULL above). */
 int gpn_lml_grad_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                          const double* variance, const double* length_scales, int nls,
                          const double* Kinv, int64_t ldk, int64_t sK, const double* at, int64_t ldat, int64_t sAt, int dy,
@@ -289,6 +307,7 @@ int gpn_lml_grad_batched(void* stream, int kind, int batch, const double* X, int
 
 /* autograd backward of gpn_kernel_matrix: out[0] = sum G*dK/dvariance,
  * out[1..nls] = sum G*dK/dlength_scales for a given dense G [n, m]. */
+/* kind: all six, GPN_SQDIST included (table at GPN_FULL above). */
 int gpn_kernel_grad(void* stream, int kind, const double* X, int64_t n, const double* X2, int64_t m, int d,
                     const double* variance, const double* length_scales, int nls,
                     const double* G, int64_t ldg, double* work, double* out);
@@ -301,6 +320,7 @@ int gpn_kernel_grad(void* stream, int kind, const double* X, int64_t n, const do
  * for a symmetric K(Z, Z) with symmetric G pass X = X2 = Z and scale = 2.
  * work: gpn_grad_x2_work_bytes(n, m, d) bytes. */
 int64_t gpn_grad_x2_work_bytes(int64_t n, int64_t m, int d);
+/* kind: all six, GPN_SQDIST included (table at GPN_FULL above). */
 int gpn_kernel_grad_x2(void* stream, int kind, const double* X, int64_t n, const double* X2, int64_t m, int d,
                        const double* variance, const double* length_scales, int nls,
                        const double* G, int64_t ldg, double scale, int accumulate,
@@ -367,7 +387,9 @@ int gpn_kernel_expr_grad(void* stream, const gpn_expr_term* terms, int nterms, c
  * rows, factorisation with fused forward substitution, reductions.  out3 as gpn_lml_reduce
  * (out3[2] = LML).  *info is cleared and set here: info > 0 => replay with noise + 10^(-10+i)
  * (functions.py:20-43).  A/winv afterwards hold L, alpha^T and the leaf inverses for the two
- * calls below. */
+ * calls below.  kind (every whole-path entry: forward, backward, refine, predict, their lock-step,
+ * ragged and piecewise forms): the five covariance functions; GPN_SQDIST: -2. */
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_lml_forward(void* stream, int kind, const double* X, int64_t n, int d,
                     const double* Y, const double* M, int dy,
                     const double* variance, const double* length_scales, int nls,
@@ -379,6 +401,7 @@ int gpn_lml_forward(void* stream, int kind, const double* X, int64_t n, int d,
  *     gpn_lml_refine_dense(stream, Ksave, lda, 0.0, n, Y, M, dy, A, lda, winv, work, out3),
  * instead of re-computing every kernel entry for its residual pass as gpn_lml_refine does (same entries bit for bit, same
  * partial sums: the same refined value).  Costs n * lda * 8 bytes of memory and a second stream of writes in the assembly. */
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_lml_forward_saving(void* stream, int kind, const double* X, int64_t n, int d,
                            const double* Y, const double* M, int dy,
                            const double* variance, const double* length_scales, int nls,
@@ -392,6 +415,7 @@ int gpn_lml_forward_saving(void* stream, int kind, const double* X, int64_t n, i
  * One assembly launch, one right-hand-side launch, the batched factorisation, one reduction launch; every model's
  * out3 / factor / info is bit-identical to gpn_lml_forward on that model alone.  info[b] > 0: replay THAT model through
  * gpn_lml_forward with noise + 10^(-10+i) (functions.py:20-43). */
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_lml_forward_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                             const double* Y, int64_t sY, const double* M, int64_t sM, int dy,
                             const double* variance, const double* length_scales, int nls, const double* noise,
@@ -414,16 +438,19 @@ int gpn_lml_forward_batched(void* stream, int kind, int batch, const double* X, 
  * gpn_lml_forward / gpn_lml_backward on the model's own n_of[b] points, provided n and all n_of[b] select the same panel levels
  * (gpn_potrf_panel_levels; both sides of 2048 rows differ) and stay below the refinement threshold.  Zero mean only (M = NULL).
  * backward work: gpn_lml_backward_batched_work_bytes(n, dy, nls, batch). */
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_lml_forward_ragged(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, const int32_t* n_of, int d,
                            const double* Y, int64_t sY, int dy,
                            const double* variance, const double* length_scales, int nls, const double* noise,
                            double* A, int64_t lda, int64_t sA, double* winv, int64_t sW, int32_t* info, double* out3);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_lml_backward_ragged(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, const int32_t* n_of, int d,
                             const double* variance, const double* length_scales, int nls,
                             const double* A, int64_t lda, int64_t sA, const double* winv, int64_t sW, int dy,
                             double* work, double* grads);
 
 int64_t gpn_lml_refine_work_bytes(int64_t n, int dy);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_lml_refine(void* stream, int kind, const double* X, int64_t n, int d,
                    const double* Y, const double* M, int dy,
                    const double* variance, const double* length_scales, int nls, const double* noise,
@@ -467,6 +494,7 @@ int gpn_gemv_t_acc(void* stream, const double* L, int64_t ld, int64_t rows, int6
                    int dy, double* c, int64_t ldc, double* work);
 int64_t gpn_refine_tile_count(int64_t n);
 int64_t gpn_refine_resid_part_work_bytes(int dy, int64_t ntiles);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_refine_resid_part(void* stream, int kind, const double* X, int64_t n, int d,
                           const double* variance, const double* length_scales, int nls, const double* noise,
                           const double* a, int dy, int64_t q0, int64_t q1, double* work, double* ka);
@@ -480,6 +508,7 @@ int gpn_refine_finish(void* stream, const double* Y, const double* M, const doub
  * grad_resid (may be NULL) [n, dy] = dLML/d(y - m) = -a.  A/winv from gpn_lml_forward with
  * info == 0; work: gpn_lml_backward_work_bytes(n, dy, nls) bytes (two factor-sized matrices). */
 int64_t gpn_lml_backward_work_bytes(int64_t n, int dy, int nls);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_lml_backward(void* stream, int kind, const double* X, int64_t n, int d,
                      const double* variance, const double* length_scales, int nls,
                      const double* A, int64_t lda, const double* winv, int dy,
@@ -494,6 +523,7 @@ int gpn_lml_backward(void* stream, int kind, const double* X, int64_t n, int d,
  * BIT-IDENTICAL per model to gpn_lml_backward on that model alone.  work: gpn_lml_backward_batched_work_bytes bytes
  * (2 factor-sized matrices per model). */
 int64_t gpn_lml_backward_batched_work_bytes(int64_t n, int dy, int nls, int batch);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_lml_backward_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                              const double* variance, const double* length_scales, int nls,
                              const double* A, int64_t lda, int64_t sA, const double* winv, int64_t sW, int dy,
@@ -522,6 +552,7 @@ int gpn_lml_kinv_batched(void* stream, int batch, int64_t n, const double* A, in
  * var = [ns] K_diag - colsumsq(A) (full_cov == 0; the reference expands it to [ns, dy])
  * or [ns, ns] K(x*) - A^T A.  work: gpn_predict_work_bytes(n, ns, dy) bytes. */
 int64_t gpn_predict_work_bytes(int64_t n, int64_t ns, int dy);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_predict(void* stream, int kind, const double* X, int64_t n, int d,
                 const double* Xs, int64_t ns, const double* Ms,
                 const double* variance, const double* length_scales, int nls,
@@ -538,6 +569,7 @@ int64_t gpn_block_inverse_bytes(int64_t n);
 int gpn_block_inverse(void* stream, const double* L, int64_t n, int64_t ldl, const double* winv, double* wb);
 int gpn_trsm_right_lt_blocked(void* stream, const double* L, int64_t n, int64_t ldl, const double* wb,
                               double* B, int64_t m, int64_t ldb, double* X, int64_t ldx);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_predict_blocked(void* stream, int kind, const double* X, int64_t n, int d,
                         const double* Xs, int64_t ns, const double* Ms,
                         const double* variance, const double* length_scales, int nls,
@@ -577,12 +609,14 @@ int64_t gpn_dist_work_bytes(int rank, int pr, int pc, int64_t n, int d, int dy, 
 /* out4 (device): [0] = sum log L_ii, [1] = |alpha|^2, [2] = LML (gpr.py:63-67), [3] = LAPACK-style
  * info of the WHOLE matrix as a double (0 = ok, j > 0 = first failing pivot: replay with
  * noise + 10^(-10+i) as functions.py:20-43 does; GPN_INFO_INTERNAL = internal failure), identical on
- * every rank.  comm may be NULL for a 1 x 1 grid.  No host synchronisation.
+ * every rank.  comm may be NULL for a 1 x 1 grid.  No host synchronisation.  kind (all four gpn_dist_* entries): the five
+ * covariance functions; GPN_SQDIST or out of range: -6.
  * out4[1] is the PLAIN |alpha|^2: from about 10^4 rows on the caller that wants north_star's 1e-8 absolute follows this call
  * with gpn_dist_lml_refine (below).
  * Errors on a multi-rank grid: a non-zero status (bad argument aside) means this rank stopped issuing the evaluation's
  * collectives part-way; its peers may be blocked inside the transport.  Nothing is drained (a collective whose peers never
  * arrive cannot complete): abort the communicators on every rank (ncclCommAbort) before reusing them. */
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -6 before any launch (table at GPN_FULL above). */
 int gpn_dist_lml_forward(void* stream, const gpn_dist_comm* comm, int rank, int pr, int pc, int kind,
                          const double* X, int64_t n, int d, const double* Y, int dy,
                          const double* variance, const double* length_scales, int nls, const double* noise,
@@ -596,6 +630,7 @@ int gpn_dist_lml_forward(void* stream, const gpn_dist_comm* comm, int rank, int 
  * grad_resid (device, [n, dy], may be NULL) = dLML/d(y - m) = -a.  Identical on every rank.  Meaningful only when
  * out4[3] == 0.  Workspace: gpn_dist_grad_work_bytes (about 3x the forward's local matrix). */
 int64_t gpn_dist_grad_work_bytes(int rank, int pr, int pc, int64_t n, int d, int dy, int64_t tile);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -6 before any launch (table at GPN_FULL above). */
 int gpn_dist_lml_grad(void* stream, const gpn_dist_comm* comm, int rank, int pr, int pc, int kind,
                       const double* X, int64_t n, int d, const double* Y, int dy,
                       const double* variance, const double* length_scales, int nls, const double* noise,
@@ -608,6 +643,7 @@ int gpn_dist_lml_grad(void* stream, const gpn_dist_comm* comm, int rank, int pr,
  * (one all-reduce of n*dy*2), finish.  At N = 65536 the plain value is 6e-8 from the CPU reference on a 1 x 2 grid and 9e-9 on
  * 2 x 4, the refined one 2-4e-9 on every grid.  rwork: gpn_dist_lml_refine_work_bytes(...) bytes, 256-byte aligned. */
 int64_t gpn_dist_lml_refine_work_bytes(int rank, int pr, int pc, int64_t n, int d, int dy, int64_t tile);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -6 before any launch (table at GPN_FULL above). */
 int gpn_dist_lml_refine(void* stream, const gpn_dist_comm* comm, int rank, int pr, int pc, int kind,
                         const double* X, int64_t n, int d, const double* Y, int dy,
                         const double* variance, const double* length_scales, int nls, const double* noise,
@@ -627,6 +663,7 @@ int gpn_dist_layout(int which, int rank, int pr, int pc, int64_t n, int d, int d
  * identical on every rank; out4 as gpn_dist_lml_forward (the reference re-factorises on every predict call as well,
  * gpr.py:104; a non-zero out4[3] is replayed with jitter by the caller).  work: gpn_dist_predict_work_bytes. */
 int64_t gpn_dist_predict_work_bytes(int rank, int pr, int pc, int64_t n, int d, int dy, int64_t ns, int64_t tile, int full_cov);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -6 before any launch (table at GPN_FULL above). */
 int gpn_dist_predict(void* stream, const gpn_dist_comm* comm, int rank, int pr, int pc, int kind,
                      const double* X, int64_t n, int d, const double* Y, int dy, const double* Xs, int64_t ns, const double* Ms,
                      const double* variance, const double* length_scales, int nls, const double* noise,
@@ -741,7 +778,8 @@ int gpn_lik_expect(void* stream, int kind, const double* params, const double* f
  * factors B = I + diag(s) K diag(s), and the gradient of the approximate evidence is sum_ij G_ij dK_ij/dtheta with an explicit
  * G.  K is never stored: every entry below re-computes it tile by tile from the points (the assembly's arithmetic, so k_ij
  * carries the bits gpn_kernel_matrix gives).  Every entry validates its arguments before any launch, adds up in a fixed order
- * without atomics (the same call twice gives the same bits) and synchronises nothing.  All vectors have n entries. */
+ * without atomics (the same call twice gives the same bits) and synchronises nothing.  All vectors have n entries.
+ * kind of gpn_laplace_system / _matvec / _diag / _grad and their lock-step forms: the five covariance functions; GPN_SQDIST: -2. */
 /* value[0] = sum_i lp_i, d1, w, d3 [n] at f [n], y [n]; each output may be NULL.  kind: GPN_LIK_PROBIT / _LOGIT / _POISSON
  * (GPN_LIK_STUDENT_T: GPN_E_UNSUPPORTED -- not log-concave).  Tail-stable closed forms (the point function of
  * gpn_lik_expect): probit through the hazard r = phi / Phi (erfcx for z < 0), d1 = t r, W = r (z + r),
@@ -752,15 +790,18 @@ int gpn_lik_derivs(void* stream, int kind, const double* f, const double* y, int
                    double* value, double* d1, double* w, double* d3);
 /* B_ij = delta_ij + s_i s_j k(x_i, x_j) into the entries on and below the diagonal of the factor buffer A (lda): the tile walk
  * and staging of gpn_kernel_matrix(GPN_LOWER); nothing above the diagonal and nothing beyond column n is written. */
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_laplace_system(void* stream, int kind, const double* X, int64_t n, int d,
                        const double* variance, const double* length_scales, int nls, const double* s, double* A, int64_t lda);
 /* out = K(X) v, matrix-free in plain fp64: one workgroup per lower 64 x 64 tile, which serves its rows and its mirror; the
  * tile partials are added per row in a fixed order.  work: gpn_laplace_rows_work_bytes(n). */
 int64_t gpn_laplace_rows_work_bytes(int64_t n);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_laplace_matvec(void* stream, int kind, const double* X, int64_t n, int d,
                        const double* variance, const double* length_scales, int nls, const double* v, double* work, double* out);
 /* sigma_i = [(K^-1 + W)^-1]_ii = (1 / s_i) sum_j K_ij s_j Binv_ji, Binv = B^-1 read from its lower triangle (ldb).  The same
  * sweep as gpn_laplace_matvec; s_i > 0.  work: gpn_laplace_rows_work_bytes(n). */
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_laplace_diag(void* stream, int kind, const double* X, int64_t n, int d,
                      const double* variance, const double* length_scales, int nls, const double* s,
                      const double* Binv, int64_t ldb, double* work, double* sigma);
@@ -768,6 +809,7 @@ int gpn_laplace_diag(void* stream, int kind, const double* X, int64_t n, int d,
  * G = 1/2 a a^T - 1/2 diag(s) Binv diag(s) + 1/2 (u d1^T + d1 u^T), never materialised: the sweep of gpn_lml_grad over the
  * lower tiles with the rank-one terms and the s_i s_j scaling in the tile epilogue.  work: gpn_laplace_grad_work_bytes(n, nls). */
 int64_t gpn_laplace_grad_work_bytes(int64_t n, int nls);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_laplace_grad(void* stream, int kind, const double* X, int64_t n, int d,
                      const double* variance, const double* length_scales, int nls, const double* s,
                      const double* Binv, int64_t ldb, const double* a, const double* u, const double* d1,
@@ -814,23 +856,27 @@ int gpn_lik_derivs_batched(void* stream, int kind, int batch, const double* f, i
                            double* work, int64_t work_bytes, double* value, double* d1, double* w, double* d3);
 /* B_b = I + diag(s_b) K_b diag(s_b), s_b = s + b*ss, into the entries on and below the diagonal of factor slot A + b*sA (the
  * layout of gpn_potrf_lower_batched); nothing outside a slot's lower triangle is written. */
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_laplace_system_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                                const double* variance, const double* length_scales, int nls, const double* s, int64_t ss,
                                double* A, int64_t lda, int64_t sA);
 /* out [batch, n]: row b = K_b v_b, v_b = v + b*sv.  work: gpn_laplace_rows_batched_work_bytes(n, batch)
  * = batch * gpn_laplace_rows_work_bytes(n). */
 int64_t gpn_laplace_rows_batched_work_bytes(int64_t n, int batch);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_laplace_matvec_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                                const double* variance, const double* length_scales, int nls, const double* v, int64_t sv,
                                double* work, double* out);
 /* sigma [batch, n]: row b = gpn_laplace_diag of model b with s_b = s + b*ss and Binv_b = Binv + b*sB (leading dimension ldb).
  * work: gpn_laplace_rows_batched_work_bytes(n, batch). */
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_laplace_diag_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                              const double* variance, const double* length_scales, int nls, const double* s, int64_t ss,
                              const double* Binv, int64_t ldb, int64_t sB, double* work, double* sigma);
 /* out [batch, 1 + nls]: row b = gpn_laplace_grad of model b; s, a, u, d1 all at stride sv, Binv_b = Binv + b*sB.
  * work: gpn_laplace_grad_batched_work_bytes(n, nls, batch) = batch * gpn_laplace_grad_work_bytes(n, nls). */
 int64_t gpn_laplace_grad_batched_work_bytes(int64_t n, int nls, int batch);
+/* kind: the five covariance functions; GPN_SQDIST or out of range: -2 before any launch (table at GPN_FULL above). */
 int gpn_laplace_grad_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                              const double* variance, const double* length_scales, int nls, const double* s,
                              const double* Binv, int64_t ldb, int64_t sB, const double* a, const double* u, const double* d1,
@@ -881,6 +927,7 @@ int gpn_loo_scale(void* stream, int64_t n, const double* Kinv, int64_t ldk, cons
  * lower tiles (K and dK re-computed from the points; any d; every native kind), Q read from its lower triangle (ldq),
  * at = a^T and wt = w^T [dy, n] (ldat, ldwt).  work: work_bytes >= gpn_loo_grad_work_bytes(n, nls). */
 int64_t gpn_loo_grad_work_bytes(int64_t n, int nls);
+/* kind: all six, GPN_SQDIST included (table at GPN_FULL above). */
 int gpn_loo_grad(void* stream, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
                  int nls, const double* Q, int64_t ldq, const double* at, int64_t ldat, const double* wt, int64_t ldwt, int dy,
                  double* work, int64_t work_bytes, double* out);
@@ -899,6 +946,7 @@ int gpn_loo_terms_batched(void* stream, int batch, int64_t n, int dy, const doub
 int gpn_loo_scale_batched(void* stream, int batch, int64_t n, const double* Kinv, int64_t ldk, int64_t sK, const double* rootd,
                           double* S, int64_t lds, int64_t sS);
 int64_t gpn_loo_grad_batched_work_bytes(int64_t n, int nls, int batch);
+/* kind: all six, GPN_SQDIST included (table at GPN_FULL above). */
 int gpn_loo_grad_batched(void* stream, int kind, int batch, const double* X, int64_t sX, int64_t n, int d, const double* variance,
                          const double* length_scales, int nls, const double* Q, int64_t ldq, int64_t sQ, const double* at,
                          int64_t ldat, int64_t sAt, const double* wt, int64_t ldwt, int64_t sWt, int dy, double* work,

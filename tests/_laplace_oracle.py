@@ -141,6 +141,11 @@ def kern(kind, X, X2, variance, ls, dt):
     elif kind == "Matern32":
         e = np.exp(-_S3 * r)
         K, B = v * (1.0 + _S3 * r) * e, 3.0 * v * e
+    elif kind in ("Exp", "Matern12"):
+        K = v * np.exp(-r)
+        B = K / r
+    elif kind == "Periodic":
+        K, B = v * np.cos(r), v * np.sin(r) / r
     else:
         raise ValueError(kind)
     return K, np.where(dead, 0.0, B)

@@ -120,6 +120,48 @@ def test_argument_validation_without_launch():
     assert lib.gpn_transpose(null, p, 0, 0, 0, p, 0) == 0
 
 
+def test_kind_validation_without_launch():
+    """every entry that factors, solves against or multiplies by K refuses GPN_SQDIST (4) like an out-of-range kind, as its first
+    check (status -2; the block-cyclic drivers: -6, their kind's position) -- gpn_kernel_matrix_batched serves it as
+    gpn_kernel_matrix does, so there kind 4 gets as far as the next bad argument."""
+    lib = _native.lib()
+    null = None
+    p = ctypes.cast(ctypes.pointer(ctypes.c_double(0.0)), ctypes.c_void_p)     # stands for a pointer that is never followed
+    for kind in (-1, 4, 6):
+        assert lib.gpn_lml_forward(null, kind, null, 4, 2, null, null, 1, null, null, 1, null, null, 128, null, null, null) == -2
+        assert lib.gpn_lml_forward_saving(null, kind, null, 4, 2, null, null, 1, null, null, 1, null, null, 128, null, null, null, null) == -2
+        assert lib.gpn_lml_forward_batched(null, kind, 2, null, 0, 4, 2, null, 0, null, 0, 1, null, null, 1, null, null, 128, 0, null, 0,
+                                           null, null) == -2
+        assert lib.gpn_lml_forward_ragged(null, kind, 2, null, 0, 1000, null, 2, null, 0, 1, null, null, 1, null, null, 1152, 0, null, 0,
+                                          null, null) == -2
+        assert lib.gpn_lml_backward(null, kind, null, 4, 2, null, null, 1, null, 128, null, 1, null, null, null) == -2
+        assert lib.gpn_lml_backward_batched(null, kind, 2, null, 0, 4, 2, null, null, 1, null, 128, 0, null, 0, 1, null, null, null) == -2
+        assert lib.gpn_lml_backward_ragged(null, kind, 2, null, 0, 1000, null, 2, null, null, 1, null, 1152, 0, null, 0, 1, null, null) == -2
+        assert lib.gpn_lml_refine(null, kind, null, 4, 2, null, null, 1, null, null, 1, null, null, 128, null, null, null) == -2
+        assert lib.gpn_refine_resid_part(null, kind, null, 4, 2, null, null, 1, null, null, 1, 0, 1, null, null) == -2
+        assert lib.gpn_predict(null, kind, null, 4, 2, null, 3, null, null, null, 1, null, 128, null, 1, 0, null, null, null) == -2
+        assert lib.gpn_predict_blocked(null, kind, null, 4, 2, null, 3, null, null, null, 1, null, 128, null, p, 1, 0, null, null, null) == -2
+        assert lib.gpn_laplace_system(null, kind, null, 4, 2, null, null, 1, null, null, 128) == -2
+        assert lib.gpn_laplace_matvec(null, kind, null, 4, 2, null, null, 1, null, null, null) == -2
+        assert lib.gpn_laplace_diag(null, kind, null, 4, 2, null, null, 1, null, null, 4, null, null) == -2
+        assert lib.gpn_laplace_grad(null, kind, null, 4, 2, null, null, 1, null, null, 4, null, null, null, null, null) == -2
+        assert lib.gpn_laplace_system_batched(null, kind, 2, null, 0, 4, 2, null, null, 1, null, 0, null, 128, 0) == -2
+        assert lib.gpn_laplace_matvec_batched(null, kind, 2, null, 0, 4, 2, null, null, 1, null, 0, null, null) == -2
+        assert lib.gpn_laplace_diag_batched(null, kind, 2, null, 0, 4, 2, null, null, 1, null, 0, null, 4, 0, null, null) == -2
+        assert lib.gpn_laplace_grad_batched(null, kind, 2, null, 0, 4, 2, null, null, 1, null, null, 4, 0, null, null, null, 0, null,
+                                            null) == -2
+        # the block-cyclic drivers on a 1 x 1 grid, which needs no communicator
+        assert lib.gpn_dist_lml_forward(null, null, 0, 1, 1, kind, null, 100, 2, null, 1, null, null, 1, null, 128, null, 0, null) == -6
+        assert lib.gpn_dist_lml_grad(null, null, 0, 1, 1, kind, null, 100, 2, null, 1, null, null, 1, null, 128, null, 0, null, null, null) == -6
+        assert lib.gpn_dist_lml_refine(null, null, 0, 1, 1, kind, null, 100, 2, null, 1, null, null, 1, null, 128, null, null, 0, null) == -6
+        assert lib.gpn_dist_predict(null, null, 0, 1, 1, kind, null, 100, 2, null, 1, p, 3, null, null, null, 1, null, 128, 0, null, 0,
+                                    null, p, p) == -6
+        # the assembly and the sweeps that have a SqDist instantiation take kind 4 and stop at their next check
+        want = -4 if kind == 4 else -2
+        assert lib.gpn_kernel_matrix_batched(null, kind, 2, null, 0, 4, null, 0, 4, 2, null, null, 1, null, 0, null, 4, 16) == want
+        assert lib.gpn_kernel_matrix(null, kind, null, 4, null, 4, 2, null, null, 1, null, 0, null, 4) == (-3 if kind == 4 else -2)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_native, "_lib", None)
     monkeypatch.setattr(_native, "LIB_PATH", str(tmp_path / "nope.so"))
