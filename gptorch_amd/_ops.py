@@ -1406,9 +1406,6 @@ class LooGroupState:
                                 self.wt, n, dy * n, dy, work=work)
 
 
-LOO_HOLDER_BUFFERS = ("loo_rhs", "loo_q", "loo_sweep")     # what a LOO group's holder keeps beside its FactorBatch (models/_lockstep.py)
-
-
 class BatchedGPRLooLik(torch.autograd.Function):
     """GPRLooLik for `batch` independent models of one shape in LOCK STEP (restarts and kernel choices of a leave-one-out fit): the
     inputs of BatchedGPRLogLik without n_of -> L_LOO [batch].  Forward: LooGroupState (gpn_lml_forward_batched, gpn_lml_kinv_batched,

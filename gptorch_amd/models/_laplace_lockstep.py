@@ -26,6 +26,7 @@ import torch
 from .. import _native, _ops
 from .._ops import _ptr, _stream
 from . import laplace
+from ._lockstep import three_padded_matrices_bytes
 from .laplace import MAX_HALVINGS, PSI_SLACK, W_FLOOR
 
 # counters for tests and tools/laplace_lockstep_bench.py: lock-step searches, Newton rounds, host reads of trial rounds, and
@@ -42,9 +43,8 @@ def supported(n):
 
 
 def per_model_bytes(n):
-    """three padded N x N matrices per model (the factor slot + the backward's two), as _lockstep._stationary_capacity counts"""
-    ld = -(-int(n) // 128) * 128 + 128
-    return 3 * 8 * (ld + 16) * ld
+    """three padded N x N matrices per model (the factor slot + the backward's two), as for a GPR model"""
+    return three_padded_matrices_bytes(n)
 
 
 class _LockstepMode(laplace._Mode):

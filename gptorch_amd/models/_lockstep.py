@@ -1,11 +1,11 @@
 """
 Several INDEPENDENT models evaluated in lock step: which models can share a call (the group keys and their memory-capacity
 rule), the buffers a group keeps between calls, and the public batched entry points batched_log_likelihood,
-batched_loss_and_grad and batched_factorise.  (GPR and VFE are imported where they are needed: models/gpr.py imports this
-module.)
+batched_loss_and_grad and batched_factorise, which are loops over FAMILIES: one entry per kind of group.
+(GPR and VFE are imported where they are needed: models/gpr.py imports this module.)
 """
 import collections
-from typing import NamedTuple, Optional
+from typing import Any, Callable, NamedTuple, Optional
 
 import torch
 
@@ -23,6 +23,64 @@ class GroupKey(NamedTuple):
     objective: str = "lml"            # what the group's models fit (GPR.objective): "loo" groups run _ops.BatchedGPRLooLik
 
 
+# The other families' keys.  Each begins with its family's name: named tuples of different classes compare as plain tuples, and
+# the key names the group's cached buffers.
+class ExprKey(NamedTuple):
+    tag: str
+    signature: tuple                  # _expr.Program.signature(): the composite kernel's structure
+    shape: tuple
+    dy: int
+    device: torch.device
+
+
+class VFEKey(NamedTuple):
+    tag: str
+    kind: str
+    shape: tuple
+    dy: int
+    nls: int
+    z_shape: tuple                    # Z's (number of inducing points, d)
+    device: torch.device
+
+
+class SiteKey(NamedTuple):
+    """LaplaceGP and EPGP groups"""
+    tag: str
+    kind: str
+    lik_kind: int
+    shape: tuple
+    nls: int
+    device: torch.device
+    H: Optional[int] = None           # EPGP: Gauss-Hermite nodes of the logit link (a group's kernel stages ONE rule), 0 for probit
+
+
+class Group(NamedTuple):
+    """the models of one list that share a lock-step call"""
+    family: "Family"
+    key: tuple                        # (key, number of models) names the group's cached buffers
+    indices: list
+    payload: Any = None               # the expression family's programs, one per model
+    priors: Optional[bool] = None     # in a plan: whether any parameter of the group's models has a prior
+
+
+class Family(NamedTuple):
+    """one kind of lock-step group (FAMILIES)"""
+    name: str
+    find: Callable                    # the grouping function: models -> [(key, indices[, payload])]
+    value: Callable                   # (ms, group, differentiable) -> the [B] lock-step values (see batched_log_likelihood)
+    keepdim: bool                     # rows as the class's own loss() returns them: (1,), else 0-dim
+    seed: Optional[Callable] = None   # (ms, group) -> number of models whose prediction caches it seeded
+    objective: str = "lml"            # the GPR.objective its groups evaluate ("lml": the value is log_likelihood())
+    held: tuple = ()                  # the tensors a group's holder keeps beside its FactorBatch "fb"
+    stacked: bool = False             # find takes for_grad=True: groups for multi_start_optimize's stacked-parameter loop
+    captured: bool = True             # under multi_start_optimize(capture=True) its models may share an evaluation
+
+    def groups(self, models, for_grad=False):
+        if for_grad:
+            return [Group(self, *found) for found in self.find(models, for_grad=True)] if self.stacked else []
+        return [Group(self, *found) for found in self.find(models)]
+
+
 # Lock-step buffers reused between calls (a search calls batched_log_likelihood / batched_loss_and_grad once per optimiser
 # step): keyed by the FULL group key + batch size -- two groups of one call can never share an entry (round-4 advice: keyed
 # by (device, batch, n, dy) only, two groups of equal count / N / dy but different kernel kind or ARD shared one buffer and
@@ -34,10 +92,10 @@ BATCH_BUFFER_MAX_BYTES = 48 << 30
 
 
 def _held_bytes():
-    # (a leave-one-out group keeps its right-hand sides, Q and the sweep's partials beside its FactorBatch; the inversion's workspace
-    #  is the FactorBatch's _backward_work)
+    # (every holder's FactorBatch -- the inversion's workspace is its _backward_work -- and what the families say their holders
+    #  keep beside it: _HELD_BESIDE_FB, from FAMILIES)
     return sum(v["fb"].nbytes() for v in _BATCH_BUFFERS.values() if "fb" in v) + \
-        sum(8 * v[name].numel() for v in _BATCH_BUFFERS.values() for name in _ops.LOO_HOLDER_BUFFERS if v.get(name) is not None)
+        sum(8 * v[name].numel() for v in _BATCH_BUFFERS.values() for name in _HELD_BESIDE_FB if v.get(name) is not None)
 
 
 def _batch_holder(key):
@@ -117,16 +175,20 @@ def _capacity(per_model, device, held=0):
     return max(2, int(LOCKSTEP_MEMORY_FRACTION * (free + held)) // per_model)
 
 
-def _stationary_capacity(n, device):
-    """... for GPR models of n rows: 3 padded N x N matrices per model (factor + the backward's two); the buffer cache's factors count
-    as free"""
+def three_padded_matrices_bytes(n):
+    """3 padded N x N matrices: what a GPR or LaplaceGP model of n rows holds in a lock-step call (factor + the backward's two)"""
     ld = -(-int(n) // 128) * 128 + 128
-    return _capacity(3 * 8 * (ld + 16) * ld, device, held=_held_bytes())
+    return 3 * 8 * (ld + 16) * ld
 
 
-def _chunks(key, g, cap):
-    """a group split into chunks of at most cap models: [(key, indices)] (singletons fall to the sequential path)"""
-    return [(key, g[at:at + cap]) for at in range(0, len(g), cap) if len(g[at:at + cap]) >= 2]
+def _chunked(groups, per_model, held=True):
+    """{key: indices} as [(key, indices)] chunks that fit the device's free memory at per_model(key) bytes a model (held: the cache's
+    buffers count as free); singletons fall to the sequential path"""
+    out = []
+    for key, g in groups.items():
+        cap = _capacity(per_model(key), key.device, held=_held_bytes() if held else 0)
+        out += [(key, g[at:at + cap]) for at in range(0, len(g), cap) if len(g[at:at + cap]) >= 2]
+    return out
 
 
 def _lockstep_groups(models, for_grad=False):
@@ -163,14 +225,14 @@ def _lockstep_groups(models, for_grad=False):
             continue
         # a lock-step group holds B factor buffers AND (with gradients) a backward workspace of two more N x N matrices per model at
         # once: groups that would not fit the device's free memory are split into chunks that do
-        out += _chunks(key, g, _stationary_capacity(key.shape[0], key.device))
+        out += _chunked({key: g}, lambda key: three_padded_matrices_bytes(key.shape[0]))
     for (common, _regime), g in pool.items():
         g = sorted(g, key=lambda i: (-models[i].X.shape[0], i))
         at = 0
         while at < len(g):
             nmax = models[g[at]].X.shape[0]
             end = at + 1
-            cap = _stationary_capacity(nmax, common.device)
+            cap = _capacity(three_padded_matrices_bytes(nmax), common.device, held=_held_bytes())
             while end < len(g) and end - at < cap and models[g[end]].X.shape[0] >= RAGGED_MIN_FRACTION * nmax:
                 end += 1
             if end - at >= 2:
@@ -200,14 +262,11 @@ def _loo_groups(models):
         if k is None or not m.X.is_cuda or not _loo_lockstep.supported(m.X.shape[0]):
             continue
         groups.setdefault(_group_key(m)._replace(objective="loo"), []).append(i)
-    out = []
-    for key, g in groups.items():
-        out += _chunks(key, g, _capacity(_loo_lockstep.per_model_bytes(key.shape[0], key.dy, key.nls), key.device, held=_held_bytes()))
-    return out
+    return _chunked(groups, lambda key: _loo_lockstep.per_model_bytes(key.shape[0], key.dy, key.nls))
 
 
 def _expression_groups(models):
-    """[(key, indices, programs)] of the GPR models over COMPOSITE kernels of one structure (equal _expr.Program.signature(),
+    """[(ExprKey, indices, programs)] of the GPR models over COMPOSITE kernels of one structure (equal _expr.Program.signature(),
     n, d, dy, device) that can share the kernel-independent launches of an evaluation (_expr.BatchedExprLogLik)."""
     from .gpr import GPR
     groups = {}
@@ -219,7 +278,7 @@ def _expression_groups(models):
         prog = m._expression(m.X)
         if prog is None:
             continue
-        key = ("expr", prog.signature(), tuple(m.X.shape), m.Y.shape[1], m.X.device)
+        key = ExprKey("expr", prog.signature(), tuple(m.X.shape), m.Y.shape[1], m.X.device)
         groups.setdefault(key, ([], []))
         groups[key][0].append(i)
         groups[key][1].append(prog)
@@ -227,10 +286,9 @@ def _expression_groups(models):
 
 
 def _vfe_groups(models):
-    """[(key, indices)] of the VFE models (sparse_gpr.py:108-153) that can share one lock-step evaluation
+    """[(VFEKey, indices)] of the VFE models (sparse_gpr.py:108-153) that can share one lock-step evaluation
     (_vfe_lockstep.BatchedVFEBound): one native stationary kind, equal (N, D, dy, M, ARD), on one device, in the single-chunk regime
-    (_vfe_lockstep.supported); split into chunks that fit the device's free memory.
-    key = ("vfe", kind, X's shape, dy, number of length scales, Z's shape, device)."""
+    (_vfe_lockstep.supported); split into chunks that fit the device's free memory (the cache's buffers do not count as free)."""
     from . import _vfe_lockstep
     from .sparse_gpr import VFE
     groups = {}
@@ -240,76 +298,76 @@ def _vfe_groups(models):
         k = m._native_kernel()
         if k is None or not m.X.is_cuda or not _vfe_lockstep.supported(m.X.shape[0], m.Z.shape[0]):
             continue
-        key = ("vfe", k._kind, tuple(m.X.shape), m.Y.shape[1], int(k.length_scales.numel()), tuple(m.Z.shape), m.X.device)
+        key = VFEKey("vfe", k._kind, tuple(m.X.shape), m.Y.shape[1], int(k.length_scales.numel()), tuple(m.Z.shape), m.X.device)
         groups.setdefault(key, []).append(i)
-    out = []
-    for key, g in groups.items():
-        _tag, _kind, (n, _d), dy, _nls, (n_inducing, _dz), device = key
-        out += _chunks(key, g, _capacity(_vfe_lockstep.per_model_bytes(n, n_inducing, dy), device))
-    return out
+    return _chunked(groups, lambda key: _vfe_lockstep.per_model_bytes(key.shape[0], key.z_shape[0], key.dy), held=False)
 
 
-def _vfe_group_bound(ms, key, differentiable):
-    """the lock-step bounds [B] of one _vfe_groups group (autograd-connected to every model's Params when differentiable)"""
-    from . import _vfe_lockstep
+def _shared_or_stacked(ms, with_y=True):
+    """(X, Y) of a group: the models' own [n, d] / [n, dy] when every model holds the same tensors (restarts on one data set; Y
+    only where X is shared too), else stacked [B, ...]"""
     m0 = ms[0]
     same_x = all(m.X.data_ptr() == m0.X.data_ptr() for m in ms)
-    same_y = same_x and all(m.Y.data_ptr() == m0.Y.data_ptr() for m in ms)
     X = m0.X if same_x else torch.stack([m.X for m in ms])
-    Y = m0.Y if same_y else torch.stack([m.Y for m in ms])               # sparse_gpr.py:125 quirk: err = Y (Zero mean only)
+    if not with_y:
+        return X, None
+    return X, m0.Y if same_x and all(m.Y.data_ptr() == m0.Y.data_ptr() for m in ms) else torch.stack([m.Y for m in ms])
+
+
+def _vfe_group_bound(ms, group, differentiable):
+    """the lock-step bounds [B] of one _vfe_groups group (autograd-connected to every model's Params when differentiable): sparse
+    models of one shape (sparse_gpr.py:108-153 in a multi-start search over inducing points / hyper-parameters)"""
+    from . import _vfe_lockstep
+    X, Y = _shared_or_stacked(ms)                                        # sparse_gpr.py:125 quirk: err = Y (Zero mean only)
     var, ls, s2 = _group_hypers(ms, differentiable)
     Z = torch.stack([m.Z for m in ms]) if differentiable else torch.stack([m.Z.data for m in ms])
-    return _vfe_lockstep.BatchedVFEBound.apply(var, ls, s2, Z, key[1], X, Y)
+    return _vfe_lockstep.BatchedVFEBound.apply(var, ls, s2, Z, group.key.kind, X, Y)
 
 
 def _laplace_key(m):
     k = m.kernel
-    return ("laplace", k._kind, m._lik_kind, tuple(m.X.shape), int(k.length_scales.numel()), m.X.device)
+    return SiteKey("laplace", k._kind, m._lik_kind, tuple(m.X.shape), int(k.length_scales.numel()), m.X.device)
+
+
+def _site_groups(models, cls, lockstep, key_of, per_model):
+    """[(key, indices)] of the cls (LaplaceGP / EPGP) models that can share one lock-step evaluation: the class's own log_likelihood
+    over points on the GPU, of a size lockstep.supported() admits, by key_of, in chunks that fit the device's free memory"""
+    groups = {}
+    for i, m in enumerate(models):
+        if not isinstance(m, cls) or type(m).log_likelihood is not cls.log_likelihood:
+            continue
+        if not (isinstance(m.X, torch.Tensor) and m.X.is_cuda) or not lockstep.supported(m.X.shape[0]):
+            continue
+        groups.setdefault(key_of(m), []).append(i)
+    return _chunked(groups, per_model)
 
 
 def _laplace_groups(models):
-    """[(key, indices)] of the LaplaceGP models that can share one lock-step evaluation (_laplace_lockstep.BatchedLaplaceEvidence):
-    LaplaceGP's own log_likelihood over points on the GPU, grouped by (kernel kind, likelihood kind, X's shape, number of length
-    scales, device) and split into chunks that fit the device's free memory; singletons stay sequential.
-    key = ("laplace", kind, likelihood kind, X's shape, number of length scales, device)."""
+    """[(SiteKey, indices)]: _site_groups of the LaplaceGP models (_laplace_lockstep.BatchedLaplaceEvidence)"""
     from . import _laplace_lockstep
     from .laplace import LaplaceGP
-    groups = {}
-    for i, m in enumerate(models):
-        if not isinstance(m, LaplaceGP) or type(m).log_likelihood is not LaplaceGP.log_likelihood:
-            continue
-        if not (isinstance(m.X, torch.Tensor) and m.X.is_cuda) or not _laplace_lockstep.supported(m.X.shape[0]):
-            continue
-        groups.setdefault(_laplace_key(m), []).append(i)
-    out = []
-    for key, g in groups.items():
-        out += _chunks(key, g, _capacity(_laplace_lockstep.per_model_bytes(key[3][0]), key[5], held=_held_bytes()))
-    return out
+    return _site_groups(models, LaplaceGP, _laplace_lockstep, _laplace_key, lambda key: _laplace_lockstep.per_model_bytes(key.shape[0]))
 
 
 def _laplace_group_inputs(ms, differentiable):
-    """(X, Y, variance [B], length scales [B, nls], [m_b = mean_function(X_b)]) of one _laplace_groups / _ep_groups group: X and Y shared when
-    every model holds the same tensors (restarts on one data set), else stacked"""
-    m0 = ms[0]
-    same_x = all(m.X.data_ptr() == m0.X.data_ptr() for m in ms)
-    same_y = same_x and all(m.Y.data_ptr() == m0.Y.data_ptr() for m in ms)
-    X = m0.X if same_x else torch.stack([m.X for m in ms])
-    Y = m0.Y if same_y else torch.stack([m.Y for m in ms])
+    """(X, Y, variance [B], length scales [B, nls], [m_b = mean_function(X_b)]) of one _laplace_groups / _ep_groups group"""
+    X, Y = _shared_or_stacked(ms)
     var = _stacked([m.kernel.variance for m in ms], differentiable).reshape(len(ms))
     ls = _stacked([m.kernel.length_scales for m in ms], differentiable).reshape(len(ms), -1)
-    if differentiable:
+    with torch.set_grad_enabled(differentiable and torch.is_grad_enabled()):
         means = [m.mean_function(m.X) for m in ms]
-    else:
-        with torch.no_grad():
-            means = [m.mean_function(m.X) for m in ms]
     return X, Y, var, ls, means
 
 
-def _laplace_group_evidence(ms, key, differentiable):
-    """the lock-step evidences [B] of one _laplace_groups group (autograd-connected to every model's Params when differentiable)"""
-    from . import _laplace_lockstep
+def _group_evidence(node, ms, key, differentiable):
+    """the lock-step evidences [B] of one LaplaceGP / EPGP group by its node (autograd-connected when differentiable)"""
     X, Y, var, ls, means = _laplace_group_inputs(ms, differentiable)
-    return _laplace_lockstep.BatchedLaplaceEvidence.apply(X, Y, var, ls, key[1], key[2], ms, _batch_holder((key, len(ms))), *means)
+    return node.apply(X, Y, var, ls, key.kind, key.lik_kind, ms, _batch_holder((key, len(ms))), *means)
+
+
+def _laplace_group_evidence(ms, group, differentiable):
+    from . import _laplace_lockstep
+    return _group_evidence(_laplace_lockstep.BatchedLaplaceEvidence, ms, group.key, differentiable)
 
 
 def _ep_key(m):
@@ -317,35 +375,19 @@ def _ep_key(m):
     link = m._lik_kind
     # (probit's moments are closed form: its models share a group whatever their likelihood's quadrature setting)
     H = 0 if link == _native.LIK_PROBIT else int(m.likelihood.num_gauss_hermite_points)
-    return ("ep", k._kind, link, tuple(m.X.shape), int(k.length_scales.numel()), m.X.device, H)
+    return SiteKey("ep", k._kind, link, tuple(m.X.shape), int(k.length_scales.numel()), m.X.device, H)
 
 
 def _ep_groups(models):
-    """[(key, indices)] of the EPGP models that can share one lock-step evaluation (_ep_lockstep.BatchedEPEvidence): EPGP's own
-    log_likelihood over points on the GPU, of a size _ep_lockstep.supported() admits, grouped and split into chunks that fit the
-    device's free memory as _laplace_groups does; singletons stay sequential.
-    key = ("ep", kind, likelihood kind, X's shape, number of length scales, device, H), H the number of Gauss-Hermite nodes of the
-    logit link (the group's kernel stages ONE rule) and 0 for probit."""
+    """[(SiteKey, indices)]: _site_groups of the EPGP models (_ep_lockstep.BatchedEPEvidence)"""
     from . import _ep_lockstep
     from .ep import EPGP
-    groups = {}
-    for i, m in enumerate(models):
-        if not isinstance(m, EPGP) or type(m).log_likelihood is not EPGP.log_likelihood:
-            continue
-        if not (isinstance(m.X, torch.Tensor) and m.X.is_cuda) or not _ep_lockstep.supported(m.X.shape[0]):
-            continue
-        groups.setdefault(_ep_key(m), []).append(i)
-    out = []
-    for key, g in groups.items():
-        out += _chunks(key, g, _capacity(_ep_lockstep.per_model_bytes(key[3][0], key[4]), key[5], held=_held_bytes()))
-    return out
+    return _site_groups(models, EPGP, _ep_lockstep, _ep_key, lambda key: _ep_lockstep.per_model_bytes(key.shape[0], key.nls))
 
 
-def _ep_group_evidence(ms, key, differentiable):
-    """the lock-step evidences [B] of one _ep_groups group (autograd-connected to every model's Params when differentiable)"""
+def _ep_group_evidence(ms, group, differentiable):
     from . import _ep_lockstep
-    X, Y, var, ls, means = _laplace_group_inputs(ms, differentiable)
-    return _ep_lockstep.BatchedEPEvidence.apply(X, Y, var, ls, key[1], key[2], ms, _batch_holder((key, len(ms))), *means)
+    return _group_evidence(_ep_lockstep.BatchedEPEvidence, ms, group.key, differentiable)
 
 
 def _group_data(ms, differentiable=False, key=None):
@@ -370,21 +412,108 @@ def _group_data(ms, differentiable=False, key=None):
         n_of = torch.tensor(key.sizes, dtype=torch.int32, device=key.device)
         holder["ragged_data"] = (stamp, X, R, n_of, [(m.X, m.Y) for m in ms])     # (holds the tensors: an id() cannot be reused)
         return X, R, n_of
-    m0 = ms[0]
-    same_x = all(m.X.data_ptr() == m0.X.data_ptr() for m in ms)
     zero_mean = all(type(m.mean_function) is mean_functions.Zero for m in ms)
-    same_r = same_x and zero_mean and all(m.Y.data_ptr() == m0.Y.data_ptr() for m in ms)
-    X = m0.X if same_x else torch.stack([m.X for m in ms])
-    if same_r:
-        R = m0.Y
-    elif zero_mean:
-        R = torch.stack([m.Y for m in ms])
-    elif differentiable:
-        R = torch.stack([m.Y - m.mean_function(m.X) for m in ms])
-    else:
-        with torch.no_grad():
+    X, R = _shared_or_stacked(ms, with_y=zero_mean)                      # (zero means: the residuals are Y itself)
+    if not zero_mean:
+        with torch.set_grad_enabled(differentiable and torch.is_grad_enabled()):
             R = torch.stack([m.Y - m.mean_function(m.X) for m in ms])
     return X, R, None
+
+
+def _lml_value(ms, group, differentiable):
+    key = group.key
+    X, R, n_of = _group_data(ms, differentiable, key=key)
+    var, ls, nz = _group_hypers(ms, differentiable)
+    holder = _batch_holder((key, len(ms)))
+    if differentiable:
+        if n_of is not None:
+            holder["sizes"] = key.sizes
+        return _ops.BatchedGPRLogLik.apply(X, R, var, ls, nz, key.kind, holder, n_of)
+    fb, terms = _ops.lml_forward_batched(key.kind, X, R, var, ls, nz, fb=holder.get("fb"),
+                                         refine=n_of is None and ms[0].X.shape[0] >= _ops.refine_min_n(), n_of=n_of)
+    holder["fb"] = fb
+
+    def finish():
+        """-> every model's (1,) row; None where the factorisation reported info != 0 (the sequential path's jitter ladder)"""
+        info = fb.info.cpu().tolist()          # one read-back per group (synchronises the stream)
+        vals = terms[:, 2:3].clone()           # ONE copy out of the shared buffers; every model gets its row of it
+        # (the per-model factor cache is NOT pointed at the shared buffer: the next batched call overwrites it)
+        return [vals[b] if info[b] == 0 else None for b in range(len(ms))]
+    return finish
+
+
+def _lml_seed(ms, group):
+    key = group.key
+    if key.sizes is not None:                  # ragged groups: a padded factor is not the layout _predict's entry points take
+        return 0
+    X, R, _ = _group_data(ms)
+    fb, _terms = _ops.lml_forward_batched(key.kind, X, R, *_group_hypers(ms), fb=None)     # buffers of their own: the caches keep them
+    info = fb.info.cpu()
+    ok = [b for b in range(len(ms)) if int(info[b]) == 0]
+    for b in ok:
+        ms[b]._seed_cached_state(key.kind, ms[b].X, fb.factor(b))
+    return len(ok)
+
+
+def _loo_value(ms, group, differentiable):
+    """leave-one-out restarts / kernel choices of one shape: L_LOO, its closed-form gradients and -w in lock step"""
+    key = group.key
+    X, R, _ = _group_data(ms, differentiable, key=key)
+    var, ls, nz = _group_hypers(ms, differentiable)
+    return _ops.BatchedGPRLooLik.apply(X, R, var, ls, nz, key.kind, _batch_holder((key, len(ms))))
+
+
+def _expr_value(ms, group, differentiable):
+    """composite kernels of one structure (the reference's example model Linear + Rbf + Constant in a multi-start search): the
+    expression's assembly and sweeps per model, everything kernel-independent once over the group"""
+    X, R, _ = _group_data(ms, differentiable)
+    nz = _stacked([m.likelihood.variance for m in ms], differentiable).reshape(len(ms))
+    flat = [p for prog in group.payload for p in prog.params()]
+    lml = _expr.BatchedExprLogLik.apply(X, R, nz, group.payload, _batch_holder((group.key, len(ms))), *flat)
+    return lml if differentiable else [lml[b:b + 1].clone() for b in range(len(ms))]       # (rows: every model its own copy)
+
+
+def _laplace_search(ms, key, X, Y, mu, var, ls, starts):
+    from . import _laplace_lockstep
+    return _laplace_lockstep.find_modes(key.kind, key.lik_kind, X, Y, mu, var, ls, starts, [m.newton_tol for m in ms], [m.max_newton_iter for m in ms])
+
+
+def _ep_search(ms, key, X, Y, mu, var, ls, starts):
+    from . import _ep_lockstep
+    return _ep_lockstep.find_sites_batched(key.kind, key.lik_kind, X, Y, mu, var, ls, ms[0]._rule(X.device), starts,
+                                           [m.ep_tol for m in ms], [m.max_sweeps for m in ms], [m.damping for m in ms])
+
+
+def _search_seed(search):
+    """LaplaceGP / EPGP folds: the searches (mode / sites) in lock step into buffers of their own; every model's prediction cache
+    gets its state, with a in the factor's extra row as the class's _mode_for_predict leaves it"""
+    def seed(ms, group):
+        key = group.key
+        X, Y, var, ls, means = _laplace_group_inputs(ms, differentiable=False)
+        n = X.shape[-2]
+        states = search(ms, key, X, Y.reshape(n) if Y.dim() == 2 else Y.reshape(len(ms), n),
+                        torch.stack([mu.reshape(n) for mu in means]), var, ls, [m._start(n) for m in ms])
+        for m, state in zip(ms, states):
+            m._remember(state)
+            state.factor.A[n, :n] = state.a
+            m._seed_cached_state((key.tag, key.kind), m.X, state)
+        return len(ms)
+    return seed
+
+
+# Every kind of lock-step group, in the order in which the entry points evaluate them (it fixes the LRU order of _BATCH_BUFFERS
+# and the order of gradient accumulation for models that share Param objects).  A new family is one more entry.
+FAMILIES = (
+    Family("lml", _lockstep_groups, _lml_value, True, seed=_lml_seed, stacked=True),
+    # (held: the right-hand sides of w, Q and the sweep's partials)
+    Family("loo", _loo_groups, _loo_value, True, objective="loo", held=("loo_rhs", "loo_q", "loo_sweep")),
+    Family("expr", _expression_groups, _expr_value, True),
+    Family("vfe", _vfe_groups, _vfe_group_bound, False),
+    # (capture=True: LaplaceGP and EPGP models keep their own optimize())
+    Family("laplace", _laplace_groups, _laplace_group_evidence, True, seed=_search_seed(_laplace_search), captured=False),
+    Family("ep", _ep_groups, _ep_group_evidence, True, seed=_search_seed(_ep_search), captured=False),
+)
+_HELD_BESIDE_FB = tuple(name for family in FAMILIES for name in family.held)
 
 
 def batched_log_likelihood(models, streams=None):
@@ -406,43 +535,16 @@ def batched_log_likelihood(models, streams=None):
     _place_all(models)
     out = [None] * len(models)
     with torch.no_grad():
-        pending = []
-        for key, g in _lockstep_groups(models):
-            ms = [models[i] for i in g]
-            X, R, n_of = _group_data(ms, key=key)
-            var, ls, nz = _group_hypers(ms)
-            holder = _batch_holder((key, len(ms)))
-            fb, terms = _ops.lml_forward_batched(key.kind, X, R, var, ls, nz, fb=holder.get("fb"),
-                                                 refine=n_of is None and ms[0].X.shape[0] >= _ops.refine_min_n(), n_of=n_of)
-            holder["fb"] = fb
-            pending.append((g, fb, terms))
-        for g, fb, terms in pending:
-            info = fb.info.cpu().tolist()          # one read-back per group (synchronises the stream)
-            vals = terms[:, 2:3].clone()           # ONE copy out of the shared buffers; every model gets its row of it
-            for b, i in enumerate(g):
-                if info[b] == 0:
-                    out[i] = vals[b]
-                    # (the per-model factor cache is NOT pointed at the shared buffer: the next batched call overwrites it)
-        for key, g, progs in _expression_groups(models):
-            ms = [models[i] for i in g]
-            X, R, _ = _group_data(ms)
-            nz = _stacked([m.likelihood.variance for m in ms]).reshape(len(ms))
-            flat = [p for prog in progs for p in prog.params()]
-            lml = _expr.BatchedExprLogLik.apply(X, R, nz, progs, _batch_holder((key, len(ms))), *flat)
-            for b, i in enumerate(g):
-                out[i] = lml[b:b + 1].clone()
-        for key, g in _vfe_groups(models):
-            elbo = _vfe_group_bound([models[i] for i in g], key, differentiable=False)
-            for b, i in enumerate(g):
-                out[i] = elbo[b]                                             # (VFE.log_likelihood returns a 0-dim tensor)
-        for key, g in _laplace_groups(models):
-            ev = _laplace_group_evidence([models[i] for i in g], key, differentiable=False)
-            for b, i in enumerate(g):
-                out[i] = ev[b:b + 1]                                         # (LaplaceGP.log_likelihood returns a (1,) tensor)
-        for key, g in _ep_groups(models):
-            ev = _ep_group_evidence([models[i] for i in g], key, differentiable=False)
-            for b, i in enumerate(g):
-                out[i] = ev[b:b + 1]                                         # (EPGP.log_likelihood returns a (1,) tensor)
+        for family in FAMILIES:
+            if family.objective != "lml":          # (log_likelihood() is the LML whatever a model fits)
+                continue
+            # Without gradients a value is the [B] tensor, the models' rows already cut, or a finisher that returns the rows (None:
+            # left to the model's own log_likelihood() below): EVERY group of the family is launched before the first finisher runs
+            launched = [(group, family.value([models[i] for i in group.indices], group, False)) for group in family.groups(models)]
+            for group, value in launched:
+                rows = value() if callable(value) else value
+                for b, i in enumerate(group.indices):
+                    out[i] = rows[b] if isinstance(rows, list) else _row(rows, b, family.keepdim)
         for i, m in enumerate(models):
             if out[i] is None:
                 out[i] = m.log_likelihood()
@@ -460,48 +562,10 @@ def batched_factorise(models):
     _place_all(models)
     seeded = 0
     with torch.no_grad():
-        for key, g in _lockstep_groups(models):
-            if key.sizes is not None:                # ragged groups: a padded factor is not the layout _predict's entry points take
-                continue
-            ms = [models[i] for i in g]
-            X, R, _ = _group_data(ms)
-            fb, _terms = _ops.lml_forward_batched(key.kind, X, R, *_group_hypers(ms), fb=None)     # buffers of their own: the caches keep them
-            info = fb.info.cpu()
-            for b, m in enumerate(ms):
-                if int(info[b]) == 0:
-                    m._seed_cached_state(key.kind, m.X, fb.factor(b))
-                    seeded += 1
-        for key, g in _laplace_groups(models):
-            # LaplaceGP folds: the mode searches in lock step into buffers of their own; every model's prediction cache gets its
-            # mode, with a^ in the factor's extra row as LaplaceGP._mode_for_predict leaves it
-            from . import _laplace_lockstep
-            ms = [models[i] for i in g]
-            X, Y, var, ls, means = _laplace_group_inputs(ms, differentiable=False)
-            n = X.shape[-2]
-            modes = _laplace_lockstep.find_modes(key[1], key[2], X, Y.reshape(n) if Y.dim() == 2 else Y.reshape(len(ms), n),
-                                                 torch.stack([mu.reshape(n) for mu in means]), var, ls, [m._start(n) for m in ms],
-                                                 [m.newton_tol for m in ms], [m.max_newton_iter for m in ms])
-            for m, mode in zip(ms, modes):
-                m._remember(mode)
-                mode.factor.A[n, :n] = mode.a
-                m._seed_cached_state(("laplace", key[1]), m.X, mode)
-                seeded += 1
-        for key, g in _ep_groups(models):
-            # EPGP folds: the EP searches in lock step into buffers of their own; every model's prediction cache gets its sites'
-            # state, with a in the factor's extra row as EPGP._mode_for_predict leaves it
-            from . import _ep_lockstep
-            ms = [models[i] for i in g]
-            X, Y, var, ls, means = _laplace_group_inputs(ms, differentiable=False)
-            n = X.shape[-2]
-            sites = _ep_lockstep.find_sites_batched(key[1], key[2], X, Y.reshape(n) if Y.dim() == 2 else Y.reshape(len(ms), n),
-                                                    torch.stack([mu.reshape(n) for mu in means]), var, ls, ms[0]._rule(X.device),
-                                                    [m._start(n) for m in ms], [m.ep_tol for m in ms], [m.max_sweeps for m in ms],
-                                                    [m.damping for m in ms])
-            for m, st in zip(ms, sites):
-                m._remember(st)
-                st.factor.A[n, :n] = st.a
-                m._seed_cached_state(("ep", key[1]), m.X, st)
-                seeded += 1
+        for family in FAMILIES:
+            if family.seed is not None:
+                for group in family.groups(models):
+                    seeded += family.seed([models[i] for i in group.indices], group)
     return seeded
 
 
@@ -510,36 +574,37 @@ def _has_priors(ms):
 
 
 def _plan_groups(models):
-    """the grouping of batched_loss_and_grad for a list of models: [(lock-step groups: the LML's and, with objective == "loo" in their key, the leave-one-out ones), (expression groups), (sparse groups),
-    (LaplaceGP and EPGP groups: their keys begin with "laplace" / "ep")] with each group's "has priors" flag.  Shapes, kernels and priors do not change while a search runs:
-    multi_start_optimize plans ONCE and hands the plan to every iteration (the grouping walks every model's parameters and, for composite kernels, rebuilds their
-    expression programs: host time that a small-N iteration would spend several times over)."""
+    """the grouping of batched_loss_and_grad for a list of models: one flat [Group] in the order of FAMILIES, each group with its
+    "has priors" flag; a family sees the models whose objective it evaluates (a model without one: "lml").  Shapes, kernels and
+    priors do not change while a search runs: multi_start_optimize plans ONCE and hands the plan to every iteration (the grouping
+    walks every model's parameters and rebuilds expression programs: host time a small-N iteration would spend several times over)."""
     _place_all(models)
-    # leave-one-out models: groups of their own (_loo_groups), travelling in the first list with objective == "loo" in their key;
-    # the other groupings do not see them (the ones no LOO group takes: their own loss(), sequentially)
-    loo = [(key, g, _has_priors([models[i] for i in g])) for key, g in _loo_groups(models)]
-    models = [m if getattr(m, "objective", "lml") == "lml" else None for m in models]
-    return ([(key, g, _has_priors([models[i] for i in g])) for key, g in _lockstep_groups(models)] + loo,
-            [(key, g, progs, _has_priors([models[i] for i in g])) for key, g, progs in _expression_groups(models)],
-            [(key, g, _has_priors([models[i] for i in g])) for key, g in _vfe_groups(models)],
-            [(key, g, _has_priors([models[i] for i in g])) for key, g in _laplace_groups(models) + _ep_groups(models)])
+    plan = []
+    objectives = [getattr(m, "objective", "lml") for m in models]          # (once: a miss on a model without the attribute is slow)
+    for family in FAMILIES:
+        own = [m if objective == family.objective else None for m, objective in zip(models, objectives)]
+        plan += [group._replace(priors=_has_priors([models[i] for i in group.indices])) for group in family.groups(own)]
+    return plan
+
+
+def _row(t, b, keepdim):
+    return t[b:b + 1] if keepdim else t[b]
 
 
 def _group_loss_and_grad(value, ms, g, priors, out, keepdim):
     """the tail of a group in batched_loss_and_grad: Model.loss (model.py:158-197) = -(value + log prior) model by model as the
     sequential code forms it, one backward for the group, every model's detached row into out ((1,) rows when keepdim: GPR;
     0-dim rows: VFE, as each class's own loss() returns them)"""
-    row = (lambda t, b: t[b:b + 1]) if keepdim else (lambda t, b: t[b])
     if priors:
         # each model's own log_prior(), added to its entry of the lock-step values exactly as Model._loss adds it
-        loss = (torch.cat if keepdim else torch.stack)([-(row(value, b) + m.log_prior()) for b, m in enumerate(ms)])
+        loss = (torch.cat if keepdim else torch.stack)([-(_row(value, b, keepdim) + m.log_prior()) for b, m in enumerate(ms)])
     else:
         loss = -(value + 0.0)                                        # model.py:_loss with an empty log prior
     if loss.requires_grad:
         loss.sum().backward()
     ld = loss.detach()
     for b, i in enumerate(g):
-        out[i] = row(ld, b)
+        out[i] = _row(ld, b, keepdim)
 
 
 def batched_loss_and_grad(models, _plan=None):
@@ -554,43 +619,16 @@ def batched_loss_and_grad(models, _plan=None):
     BIT-IDENTICAL to its own `loss(); backward()`; a model whose factorisation fails is replayed alone through the jitter
     ladder; parameters with priors add their model's own log_prior() (model.py:158-197); sizes that refine the quadratic
     form refine it per model.  Composite / dense-K kernels and singletons take the sequential path.  Equal-shape
-    GPR(objective="loo") models run in lock step too (_loo_groups, _ops.BatchedGPRLooLik: they travel in the plan's first list with
-    objective == "loo" in their key), each model's loss and gradients bit-identical to its own evaluation.  Equal-shape LaplaceGP models
+    GPR(objective="loo") models run in lock step too (_loo_groups, _ops.BatchedGPRLooLik: the plan's "loo" groups), each model's
+    loss and gradients bit-identical to its own evaluation.  Equal-shape LaplaceGP models
     run their mode searches, evidences and closed-form gradients in lock step too (_laplace_groups, models/_laplace_lockstep.py),
     each model's loss, gradients, warm-start mode and newton_stats bit-identical to its own evaluation; so do equal-shape EPGP
     models (_ep_groups, models/_ep_lockstep.py): loss, gradients, sites and ep_stats bit-identical per model."""
     plan = _plan if _plan is not None else _plan_groups(models)
     out = [None] * len(models)
-    for key, g, priors in plan[0]:
-        ms = [models[i] for i in g]
-        X, R, n_of = _group_data(ms, differentiable=True, key=key)
-        var, ls, nz = _group_hypers(ms, differentiable=True)
-        holder = _batch_holder((key, len(ms)))
-        if key.objective == "loo":
-            # leave-one-out restarts / kernel choices of one shape: L_LOO, its closed-form gradients and -w in lock step
-            _group_loss_and_grad(_ops.BatchedGPRLooLik.apply(X, R, var, ls, nz, key.kind, holder), ms, g, priors, out, True)
-            continue
-        if n_of is not None:
-            holder["sizes"] = key.sizes
-        _group_loss_and_grad(_ops.BatchedGPRLogLik.apply(X, R, var, ls, nz, key.kind, holder, n_of), ms, g, priors, out, True)
-    for key, g, progs, priors in plan[1]:
-        # composite kernels of one structure (the reference's example model Linear + Rbf + Constant in a multi-start search):
-        # the expression's assembly and sweeps per model, everything kernel-independent once over the group
-        ms = [models[i] for i in g]
-        X, R, _ = _group_data(ms, differentiable=True)
-        nz = _stacked([m.likelihood.variance for m in ms], differentiable=True).reshape(len(ms))
-        flat = [p for prog in progs for p in prog.params()]
-        lml = _expr.BatchedExprLogLik.apply(X, R, nz, progs, _batch_holder((key, len(ms))), *flat)
-        _group_loss_and_grad(lml, ms, g, priors, out, True)
-    for key, g, priors in plan[2]:
-        # sparse models of one shape (sparse_gpr.py:108-153 in a multi-start search over inducing points / hyper-parameters)
-        ms = [models[i] for i in g]
-        _group_loss_and_grad(_vfe_group_bound(ms, key, differentiable=True), ms, g, priors, out, False)
-    for key, g, priors in plan[3]:
-        # LaplaceGP / EPGP restarts / folds of one shape: the searches, evidences and closed-form gradients in lock step
-        ms = [models[i] for i in g]
-        evidence = _ep_group_evidence if key[0] == "ep" else _laplace_group_evidence
-        _group_loss_and_grad(evidence(ms, key, differentiable=True), ms, g, priors, out, True)
+    for group in plan:
+        ms = [models[i] for i in group.indices]
+        _group_loss_and_grad(group.family.value(ms, group, True), ms, group.indices, group.priors, out, group.family.keepdim)
     for i, m in enumerate(models):
         if out[i] is None:
             loss = m.loss()

@@ -6,8 +6,8 @@ host thread and one batched evaluation per round.
 import torch
 
 from .. import _ops
-from ._lockstep import (_ep_groups, _expression_groups, _group_data, _group_param_lists, _laplace_groups, _lockstep_groups, _place_all,
-                        _plan_groups, _shared_transform, _vfe_groups, batched_loss_and_grad, release_batch_buffers)
+from ._lockstep import (FAMILIES, _group_data, _group_param_lists, _lockstep_groups, _place_all, _plan_groups, _shared_transform,
+                        batched_loss_and_grad, release_batch_buffers)
 from .base import _SCIPY_METHODS, _TORCH_DEFAULT_LR
 
 
@@ -263,10 +263,10 @@ def multi_start_optimize(models, method="Adam", max_iter=2000, verbose=False, le
             done[i] = True
     rest = [i for i in range(len(models)) if not done[i]]
     rest_models = [models[i] for i in rest]
-    if method in _TORCH_DEFAULT_LR and method != "LBFGS" and len(rest) >= 2 and \
-            (_lockstep_groups(rest_models) or _expression_groups(rest_models) or _vfe_groups(rest_models) or
-             (not capture and (_laplace_groups(rest_models) or _ep_groups(rest_models)))):
-        # (capture=True: LaplaceGP and EPGP models keep their own optimize())
+    # (any family that evaluates log_likelihood() taking a group of the list AS IT IS -- not of the plan's view, in which a
+    #  leave-one-out model enters LOO groups only; capture=True: LaplaceGP and EPGP models keep their own optimize())
+    sharing = [f for f in FAMILIES if f.objective == "lml" and (f.captured or not capture)]
+    if method in _TORCH_DEFAULT_LR and method != "LBFGS" and len(rest) >= 2 and any(f.groups(rest_models) for f in sharing):
         # What cannot share a stacked parameter tensor (composite kernels, priors, trainable mean functions, mixed frozen
         # parameters) still shares the EVALUATION: every model keeps its own optimiser over its own parameters -- exactly the
         # objects and tensor layouts of its own optimize(), so its trajectory is bit-identical -- and each iteration is one

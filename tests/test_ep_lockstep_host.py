@@ -102,8 +102,8 @@ def test_grouping_on_the_host():
               _ep(30, kernels.Rbf(2, ARD=True), likelihoods.Bernoulli("probit")),         # ARD
               _ep(31, kernels.Rbf(2), likelihoods.Bernoulli("probit"))]                   # N
     keys = [_lockstep._ep_key(m) for m in [base[0]] + others]
-    assert len(set(keys)) == len(keys) and all(k[0] == "ep" for k in keys)
-    assert keys[1][-1] == 20 and keys[2][-1] == 32 and keys[0][-1] == 0
+    assert len(set(keys)) == len(keys) and all(k.tag == "ep" for k in keys)
+    assert keys[1].H == 20 and keys[2].H == 32 and keys[0].H == 0
     # probit's moments are closed form: models that differ in the likelihood's quadrature setting alone stay together
     assert _lockstep._ep_key(_ep(30, kernels.Rbf(2), likelihoods.Bernoulli("probit"), H=32)) == keys[0]
     # LaplaceGP models never enter an EP group, whatever else the list holds
@@ -112,7 +112,7 @@ def test_grouping_on_the_host():
     assert _lockstep._ep_groups(lap + base) == []
     assert not any(isinstance(m, EPGP) for m in lap) and not any(isinstance(m, LaplaceGP) for m in base)
     plan = _lockstep._plan_groups(lap + base)
-    assert len(plan) == 4 and plan[3] == []
+    assert isinstance(plan, list) and not [grp for grp in plan if grp.family.name in ("laplace", "ep")]
     assert el.supported(1) and el.supported(512) and el.supported(el.MAX_N) and not el.supported(0) and not el.supported(el.MAX_N + 1)
 
 

@@ -326,8 +326,8 @@ def test_mixed_list(device):
         return [probit[0], g[0], lap[0], h20[0], h32[0], probit[1], g[1], lap[1], h20[1], h32[1]]
     lock, alone = build(), build()
     plan = _lockstep._plan_groups(lock)
-    assert [len(p) for p in plan] == [1, 0, 0, 4]
-    assert sorted((key[0], key[-1] if key[0] == "ep" else None, g) for key, g, _ in plan[3]) == \
+    assert [grp.family.name for grp in plan] == ["lml", "laplace", "ep", "ep", "ep"]
+    assert sorted((grp.family.name, getattr(grp.key, "H", None), grp.indices) for grp in plan[1:]) == \
         [("ep", 0, [0, 5]), ("ep", 20, [3, 8]), ("ep", 32, [4, 9]), ("laplace", None, [2, 7])]
     want = _evaluate_alone(alone)
     for mdl in lock:
@@ -348,12 +348,13 @@ def test_backward_survives_a_later_forward(device):
     check), and its gradients are those taken immediately"""
     lock = _restarts("probit_rbf_300x2", SETTINGS, mean=0.2)
     (key, g), = _lockstep._ep_groups(lock)
+    group = _lockstep.Group(None, key, g)
 
     def forward():
         for mdl in lock:
             mdl.reset_sites()
             mdl.zero_grad()
-        return -_lockstep._ep_group_evidence(lock, key, differentiable=True)
+        return -_lockstep._ep_group_evidence(lock, group, differentiable=True)
 
     def grads():
         return [p.grad.clone() for mdl in lock for p in mdl.parameters() if p.grad is not None]
@@ -367,7 +368,7 @@ def test_backward_survives_a_later_forward(device):
             mdl.kernel.variance.data += 0.1
     for mdl in lock:
         mdl.reset_sites()
-    later = -_lockstep._ep_group_evidence(lock, key, differentiable=True)  # refactorises the shared slots at other parameters
+    later = -_lockstep._ep_group_evidence(lock, group, differentiable=True)  # refactorises the shared slots at other parameters
     assert not torch.equal(later.detach(), first.detach())
     with torch.no_grad():
         for mdl in lock:

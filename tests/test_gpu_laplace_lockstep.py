@@ -327,7 +327,7 @@ def test_mixed_list(device):
         return [lap[0], g[0], v[0], lone[0], lap[1], g[1], v[1]]
     lock, alone = build(), build()
     plan = _lockstep._plan_groups(lock)
-    assert [len(p) for p in plan] == [1, 0, 1, 1] and plan[3][0][1] == [0, 4]
+    assert [grp.family.name for grp in plan] == ["lml", "vfe", "laplace"] and plan[-1].indices == [0, 4]
     want = _evaluate_alone(alone)
     for mdl in lock:
         mdl.zero_grad()

@@ -215,7 +215,7 @@ def case_restarts(name, count=3):
 
 def loo_plan(ms):
     plan = _lockstep._plan_groups(ms)
-    assert len(plan) == 4
+    assert all(isinstance(grp, _lockstep.Group) for grp in plan)
     return plan
 
 
@@ -226,7 +226,7 @@ def test_group_of_restarts_gets_each_models_own_bits(device, name):
     ms = case_restarts(name)
     want = own_evaluation(ms)
     plan = loo_plan(ms)
-    assert [len(p) for p in plan] == [1, 0, 0, 0] and plan[0][0][0].objective == "loo" and plan[0][0][1] == [0, 1, 2]
+    assert [grp.family.name for grp in plan] == ["loo"] and plan[0].key.objective == "loo" and plan[0].indices == [0, 1, 2]
     losses = batched_loss_and_grad(ms)
     assert_own_bits(ms, losses, want)
     # ... and again from the cached buffers (the second call of a search)
@@ -250,7 +250,7 @@ def test_golden_case_as_a_group_of_two(device, name):
     case = CASES[name]
     e = case["e64"]
     ms = [build_model(case), build_model(case)]
-    assert len(loo_plan(ms)[0]) == 1
+    assert [grp.family.name for grp in loo_plan(ms)] == ["loo"]
     losses = batched_loss_and_grad(ms)
     for m, loss in zip(ms, losses):
         err = xr.rel_err(loss.item(), case["loss"])
@@ -285,8 +285,9 @@ def test_a_failing_model_is_replayed_alone(device):
     want = own_evaluation(ms)
     assert ms[2]._holder["factor"].jitter_rung >= 0
     plan = loo_plan(ms)
-    key, g, _priors = plan[0][0]
-    assert g == [0, 1, 2, 3] and key.objective == "loo"
+    (group,) = plan
+    key, g = group.key, group.indices
+    assert g == [0, 1, 2, 3] and key.objective == "loo" and group.family.name == "loo"
     losses = batched_loss_and_grad(ms, _plan=plan)
     replayed = _lockstep._BATCH_BUFFERS[(key, 4)]["loo_replayed"]
     assert list(replayed) == [2] and replayed[2] >= 0 and replayed[2] == ms[2]._holder["factor"].jitter_rung
@@ -302,7 +303,7 @@ def test_a_noise_prior_enters_its_models_loss_once(device):
     ms[1].likelihood.variance.prior = prior
     want = own_evaluation(ms)
     plan = loo_plan(ms)
-    assert plan[0][0][2] is True                                  # the group's "has priors" flag
+    assert plan[0].priors is True                                 # the group's "has priors" flag
     losses = batched_loss_and_grad(ms, _plan=plan)
     lp = prior.log_prob(ms[1].likelihood.variance.transform()).sum().detach()
     assert lp.item() != 0.0 and torch.equal(losses[1], -(-plain[1] + lp))
@@ -332,10 +333,10 @@ def test_a_mixed_list(device):
     want = own_evaluation(mixed_list())
     ms = mixed_list()
     plan = loo_plan(ms)
-    assert [len(p) for p in plan] == [2, 0, 0, 1]
-    by_objective = {key.objective: g for key, g, _ in plan[0]}
+    assert [grp.family.name for grp in plan] == ["lml", "loo", "laplace"]
+    by_objective = {grp.key.objective: grp.indices for grp in plan[:2]}
     assert by_objective == {"lml": [0, 3], "loo": [1, 6]}
-    assert plan[3][0][1] == [5, 7]
+    assert plan[2].indices == [5, 7]
     losses = batched_loss_and_grad(ms, _plan=plan)
     assert_own_bits(ms, losses, want)
 
@@ -393,7 +394,7 @@ def test_backward_survives_a_later_forward(device):
     stamp has moved, the node rebuilds its state privately, and the gradients are those of the first."""
     ms = case_restarts("matern52_ard_257x3")
     want = own_evaluation(ms)
-    key = loo_plan(ms)[0][0][0]
+    key = loo_plan(ms)[0].key
     holder = _lockstep._batch_holder((key, len(ms)))
 
     def forward():
@@ -447,6 +448,6 @@ def test_the_lockstep_path_runs(device, monkeypatch):
         with pytest.raises(AssertionError, match="single-model"):
             batched_loss_and_grad(ms[:1])
     ms[0].zero_grad()
-    assert loo_plan(ms[:1])[0] == []
+    assert [grp for grp in loo_plan(ms[:1]) if grp.family.name in ("lml", "loo")] == []
     alone = batched_loss_and_grad(ms[:1])
     assert_own_bits(ms[:1], alone, want[:1])

@@ -132,12 +132,12 @@ def test_grouping_on_the_host():
     keys = [_lockstep._laplace_key(m) for m in [base[0]] + others]
     assert len(set(keys)) == len(keys)
     assert ll.supported(1) and ll.supported(512) and not ll.supported(0)
-    assert ll.per_model_bytes(300) == 3 * 8 * (512 + 16) * 512              # three padded N x N matrices, as _stationary_capacity counts
-    # a GPR / VFE list: the first three entries of the plan are what they were, the fourth is empty
+    assert ll.per_model_bytes(300) == 3 * 8 * (512 + 16) * 512              # three padded N x N matrices, as for a GPR model
+    # a GPR / VFE list with the CPU-resident LaplaceGP models: the plan is what every family takes from it, one after the other,
+    # each group with its priors flag -- and it holds no laplace or ep group
     x, y = rng.make_regression(40, 2, 1, seed=3)
     ms = [GPR(x, y, kernels.Rbf(2)) for _ in range(2)] + [VFE(x, y, kernels.Rbf(2), inducing_points=x[:8]) for _ in range(2)]
     plan = _lockstep._plan_groups(ms + base)
-    assert len(plan) == 4 and plan[3] == []
-    assert plan[:3] == ([(k, g, _lockstep._has_priors([ms[i] for i in g])) for k, g in _lockstep._lockstep_groups(ms)],
-                        [(k, g, p, _lockstep._has_priors([ms[i] for i in g])) for k, g, p in _lockstep._expression_groups(ms)],
-                        [(k, g, _lockstep._has_priors([ms[i] for i in g])) for k, g in _lockstep._vfe_groups(ms)])
+    assert plan == [grp._replace(priors=_lockstep._has_priors([(ms + base)[i] for i in grp.indices]))
+                    for family in _lockstep.FAMILIES for grp in family.groups(ms + base)]
+    assert not [grp for grp in plan if grp.family.name in ("laplace", "ep")]

@@ -1,10 +1,12 @@
 """Leave-one-out GPR in lock step, the part that needs no GPU: the argument validation of the three gpn_loo_*_batched entry points (no
 launch), their work-size functions against the single ones, the memory one model of a group is charged, the size rule, and the
-group key's new last field."""
+group key's new last field -- and the table of lock-step families with every family's key."""
 import ctypes
 
-from gptorch_amd import _native, _ops, kernels, rng
-from gptorch_amd.models import GPR, _lockstep, _loo_lockstep
+import numpy as np
+
+from gptorch_amd import _native, _ops, kernels, likelihoods, rng
+from gptorch_amd.models import EPGP, GPR, VFE, LaplaceGP, _laplace_lockstep, _lockstep, _loo_lockstep
 
 
 def _host_pointer():
@@ -142,9 +144,47 @@ def test_group_key_keeps_its_positions():
     assert key._replace(objective="loo") != key
 
 
-def test_plan_of_cpu_models_has_four_lists():
+def test_plan_of_cpu_models_is_an_empty_list():
     x, y = rng.make_regression(20, 2, 1, seed=5)
     ms = [GPR(x, y, kernels.Rbf(2), objective="loo"), GPR(x, y, kernels.Rbf(2), objective="loo"), GPR(x, y, kernels.Rbf(2))]
-    plan = _lockstep._plan_groups(ms)
-    assert len(plan) == 4 and [len(p) for p in plan] == [0, 0, 0, 0]
+    assert _lockstep._plan_groups(ms) == []
     assert _lockstep._loo_groups(ms) == []
+
+
+def test_family_table_on_cpu_models():
+    """one CPU-resident model of each family: no family takes any of them, the table is the six families in the order in which
+    the entry points evaluate them, and every family's key is a hashable named tuple whose fields have names"""
+    x, y = rng.make_regression(20, 2, 1, seed=5)
+    labels = (np.asarray(y) > 0).astype(np.float64)
+    composite = GPR(x, y, kernels.Rbf(2) + kernels.Matern52(2))
+    vfe = VFE(x, y, kernels.Rbf(2), inducing_points=x[:8])
+    laplace = LaplaceGP(x, labels, kernels.Rbf(2), likelihoods.Bernoulli("probit"))
+    ep = EPGP(x, labels, kernels.Rbf(2), likelihoods.Bernoulli("logit"))
+    ms = [GPR(x, y, kernels.Rbf(2)), GPR(x, y, kernels.Rbf(2), objective="loo"), composite, vfe, laplace, ep]
+    assert _lockstep._plan_groups(ms) == []
+    assert [family.name for family in _lockstep.FAMILIES] == ["lml", "loo", "expr", "vfe", "laplace", "ep"]
+    for family in _lockstep.FAMILIES:
+        assert family.groups(ms) == [] and family.groups(ms, for_grad=True) == [], family.name
+    prog = composite.kernel.fused_program()                                   # (GPR._expression hands it out on the GPU only)
+    keys = {"lml": _lockstep._group_key(ms[0]),
+            "loo": _lockstep._group_key(ms[1])._replace(objective="loo"),
+            "expr": _lockstep.ExprKey("expr", prog.signature(), tuple(composite.X.shape), 1, composite.X.device),
+            "vfe": _lockstep.VFEKey("vfe", "Rbf", tuple(vfe.X.shape), 1, 1, tuple(vfe.Z.shape), vfe.X.device),
+            "laplace": _lockstep._laplace_key(laplace),
+            "ep": _lockstep._ep_key(ep)}
+    fields = {"lml": ("kind", "shape", "dy", "nls", "device", "sizes", "objective"),
+              "expr": ("tag", "signature", "shape", "dy", "device"),
+              "vfe": ("tag", "kind", "shape", "dy", "nls", "z_shape", "device"),
+              "laplace": ("tag", "kind", "lik_kind", "shape", "nls", "device", "H")}
+    fields["loo"], fields["ep"] = fields["lml"], fields["laplace"]
+    assert sorted(keys) == sorted(family.name for family in _lockstep.FAMILIES)
+    for name, key in keys.items():
+        assert isinstance(key, tuple) and key._fields == fields[name], name
+        assert all(getattr(key, field) == value for field, value in zip(key._fields, key)), name
+        assert hash(key) == hash(tuple(key)) and {key: 1}[key] == 1, name
+    assert len({tuple(key) for key in keys.values()}) == 6          # (no two families' keys compare equal)
+    assert keys["expr"].tag == "expr" and keys["vfe"].tag == "vfe" and keys["laplace"].tag == "laplace" and keys["ep"].tag == "ep"
+    assert keys["loo"].objective == "loo" and keys["vfe"].z_shape == (8, 2) and keys["ep"].H == ep.likelihood.num_gauss_hermite_points
+    assert keys["laplace"].H is None and type(keys["laplace"]) is type(keys["ep"]) is _lockstep.SiteKey
+    # the one byte count of three padded N x N matrices serves the stationary capacity rule and LaplaceGP's
+    assert _lockstep.three_padded_matrices_bytes(300) == 3 * 8 * (512 + 16) * 512 == _laplace_lockstep.per_model_bytes(300)

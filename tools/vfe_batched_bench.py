@@ -96,7 +96,7 @@ for case in cases:
         def fwd():
             with torch.no_grad():
                 for key, g in gpr_mod._vfe_groups(ms):
-                    gpr_mod._vfe_group_bound([ms[i] for i in g], key, differentiable=False)
+                    gpr_mod._vfe_group_bound([ms[i] for i in g], gpr_mod.Group(None, key, g), differentiable=False)
         t_f = wall(fwd, steps)
         print("    parts: forward %.3f ms, backward + autograd plumbing %.3f ms" % (1e3 * t_f, 1e3 * (e_lock - t_f)), flush=True)
     del ms, opts
