@@ -1,9 +1,13 @@
 """
-TEST INFRASTRUCTURE ONLY -- long-double statements of the two sparse bounds, their gradients and predictions.
+TEST INFRASTRUCTURE ONLY -- long-double statements of the two sparse bounds and of the FITC likelihood, their gradients
+and predictions.
 
     VFERef    the collapsed bound of sparse_gpr.py:108-153 (Titsias), predict_f of 155-195
     SVGPRef   q(f)'s marginals, KL(q(u) || p(u)), the minibatch-scaled Gaussian data term and the bound of
               sparse_gpr.py:198-381
+    FITCRef   the marginal likelihood of gptorch_amd/models/_fitc.py's header in its whitened form (A = L^-1 Kuf,
+              lambda = Kdiag - colsum(A^2) + s, B = I + A D A^T, c = LB^-1 A D err) and the collapsed predictions; its
+              gradients by matrix calculus on (A, lambda, err), NOT the collapsed S of _fitc.py
 
 Everything is numpy long double on top of tests/_xref.py (direct-difference distances with the reference's clamp, its
 Cholesky and triangular solves, its closed-form kernel pull-backs).  Nothing here is shared with gptorch_amd.  The
@@ -17,8 +21,9 @@ Parameters are the constrained values; gradients are of the LOSS (minus the boun
 see: the log of every positive value, the mean and Z as they are, and for q_sqrt the strictly-lower entries as they
 are with the log of the diagonal.
 
-Direct64VFE / Direct64SVGP are the plain fp64 evaluations (the reference's op chain in torch on the CPU, K by direct
-differences, gradients by autograd) whose distance from the long-double value is the e64 of tests/_xref.tol.
+Direct64VFE / Direct64SVGP / Direct64FITC are the plain fp64 evaluations (the reference's op chain in torch on the CPU
+-- FITC: the M-sized Woodbury form of tests/_fitc_oracle.py --, K by direct differences, gradients by autograd) whose
+distance from the long-double value is the e64 of tests/_xref.tol.
 
 `plant=` evaluates a reference WITH one deliberate mistake, for the resolving-power tests only:
     VFE   "drop_last_row"     the last row of x is missing from A A^T and A err (N, |err|^2 and tr Kff still count it)
@@ -28,6 +33,11 @@ differences, gradients by autograd) whose distance from the long-double value is
     SVGP  "scale_one"         the minibatch scale num_data / rows replaced by 1
           "gq_triangle"       G_Q = alpha^T diag(g_var) alpha held as its lower triangle only (not mirrored)
           "drop_kd_diag"      the -dy / diag(S_L) term of d KL / d S_L dropped
+    FITC  "drop_last_row"     the last row of x is missing from A D A^T and A D err (sum log lambda, sum err^2 / lambda still count it)
+          "sums_first_chunk"  sum log lambda_i and sum err_i^2 / lambda_i over the first plant_at rows only (one chunk's slot lost)
+          "aga_triangle"      the A diag(g) A^T part of T = G_A A^T held as its lower triangle only, where Psi mirrors it
+          "drop_kdiag_grad"   the dF/dKdiag pull-back dropped
+          "g_without_h"       g_i without its a_i^T B^-1 a_i / lambda_i^2 term
 """
 import math
 
@@ -35,6 +45,7 @@ import numpy as np
 import torch
 
 from oracle import gp_oracle as orc
+from tests import _fitc_oracle as fo
 from tests import _svgp_oracle as so
 from tests import _xref as xr
 
@@ -313,6 +324,105 @@ class SVGPRef:
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# FITC
+# ---------------------------------------------------------------------------------------------------------------------
+FITC_PLANTS = ("drop_last_row", "sums_first_chunk", "aga_triangle", "drop_kdiag_grad", "g_without_h")
+
+
+class FITCRef:
+    """the F of gptorch_amd/models/_fitc.py's header, whitened: A = L^-1 Kuf, lambda = Kdiag - colsum(A^2) + s,
+    B = I + A D A^T (D = diag(1 / lambda)), c = LB^-1 A D err."""
+
+    def __init__(self, x, y, z, kernel, noise, mean=None, jitter=0.0, plant=None, plant_at=0):
+        self.X, self.Y, self.Z = xr.ld(x), xr.ld(y), xr.ld(z)
+        self.n, self.p = self.Y.shape
+        self.m = self.Z.shape[0]
+        self.spec = spec_of(kernel, self.X.shape[1]) if isinstance(kernel, dict) else kernel
+        self.s = LD(noise)
+        self.mean = np.zeros(self.p, dtype=LD) if mean is None else xr.ld(mean)
+        self.err = self.Y - self.mean
+        if plant is not None and plant not in FITC_PLANTS:
+            raise ValueError(plant)
+        self.plant = plant
+        # mask_c: the columns of A that enter A D A^T and A D err; mask_s: the rows counted in sum log lambda and sum err^2 / lambda
+        self.mask_c, self.mask_s = np.ones(self.n, dtype=LD), np.ones(self.n, dtype=LD)
+        if plant == "drop_last_row":
+            self.mask_c[-1] = 0
+        elif plant == "sums_first_chunk":
+            self.mask_s[plant_at:] = 0
+        self.Kuu = xr.expr_K(self.spec, self.Z, None) + LD(jitter) * np.eye(self.m, dtype=LD)
+        self.Kuf = xr.expr_K(self.spec, self.Z, self.X)
+        self.L = xr.cholesky(self.Kuu)
+        self.A = xr.solve_lower(self.L, self.Kuf)
+        self.lam = xr.expr_Kdiag(self.spec, self.X) - np.sum(self.A * self.A, 0) + self.s
+        self.Ac = self.A * self.mask_c
+        self.B = np.eye(self.m, dtype=LD) + (self.Ac / self.lam) @ self.Ac.T
+        self.LB = xr.cholesky(self.B)
+        self.b = (self.Ac / self.lam) @ self.err
+        self.c = xr.solve_lower(self.LB, self.b)
+
+    def lml(self):
+        n, p = self.n, self.p
+        return (-LD(0.5) * p * n * LOG2PI - LD(0.5) * p * np.sum(self.mask_s * np.log(self.lam)) - p * np.sum(np.log(np.diag(self.LB)))
+                - LD(0.5) * np.sum(self.mask_s * np.sum(self.err ** 2, 1) / self.lam) + LD(0.5) * np.sum(self.c ** 2))
+
+    def loss(self):
+        return -self.lml()
+
+    def loss_grads(self, with_Z=True):
+        """-> {variance, length_scales (composite: + linear_variance, constant), noise, mean, Z}: d loss / d raw.
+
+        F as a function of (A_c, lambda, err), A_c the columns of A that enter B and b (all of them unless planted), beta = B^-1 b,
+        q_i = A_c,i^T beta, h_i = A_c,i^T B^-1 A_c,i, from dB = dA_c D A_c^T + A_c D dA_c^T + A_c dD A_c^T, db = dA_c D err + A_c dD err:
+            dF/dA_c      = [beta (err - A_c^T beta)^T - p B^-1 A_c] D                                    (lambda held fixed)
+            dF/dlambda_i = -p/(2 lambda_i) + p h_i/(2 lambda_i^2) + (|err_i|^2 - 2 q_i.err_i + |q_i|^2)/(2 lambda_i^2)   (= g_i / 2)
+            dF/derr_i    = -(err_i - q_i)/lambda_i
+        lambda_i = Kdiag_i - |a_i|^2 + s hands dF/dlambda on: dF/dKdiag_i = dF/dlambda_i, dF/ds = their sum, and -2 A diag(dF/dlambda)
+        joins dF/dA_c in G_A (M x N).  A = L^-1 Kuf is pulled back as in VFERef.loss_grads: dKuf = L^-T G_A and, with T = G_A A^T formed
+        as it stands, dKuu = -L^-T Psi(T) L^-1, Psi(T) = 1/2 (strict lower + its mirror + diagonal)."""
+        n, p, m, s, lam = self.n, self.p, self.m, self.s, self.lam
+        eye = np.eye(m, dtype=LD)
+        Li = xr.solve_lower(self.L, eye)
+        Binv = _inverse_from_factor(self.LB)[1]
+        A, Ac, mc, ms = self.A, self.Ac, self.mask_c, self.mask_s
+        beta = Binv @ self.b
+        q = Ac.T @ beta                                                    # [n, p]
+        h = np.sum(Ac * (Binv @ Ac), 0)
+        if self.plant == "g_without_h":
+            h = np.zeros(n, dtype=LD)
+        g_lam = (-LD(0.5) * p * ms / lam + LD(0.5) * p * h / lam ** 2
+                 + LD(0.5) * (ms * np.sum(self.err ** 2, 1) - 2 * np.sum(q * self.err, 1) + np.sum(q * q, 1)) / lam ** 2)
+        GA_c = ((beta @ (self.err - q).T - p * (Binv @ Ac)) / lam) * mc
+        GA_lam = -2 * A * g_lam
+        GA = GA_c + GA_lam
+        psi = lambda T: LD(0.5) * (np.tril(T, -1) + np.tril(T, -1).T + np.diag(np.diag(T)))
+        if self.plant == "aga_triangle":
+            Psi = psi(GA_c @ A.T) + LD(0.5) * np.tril(GA_lam @ A.T)
+        else:
+            Psi = psi(GA @ A.T)
+        Guu = -Li.T @ Psi @ Li
+        Guf = Li.T @ GA
+        g_err = -(ms[:, None] * self.err - q) / lam[:, None]
+        g_kd = np.zeros(n, dtype=LD) if self.plant == "drop_kdiag_grad" else g_lam
+        out = _kernel_grads(self.spec, [(self.Z, None, Guu), (self.Z, self.X, Guf)], [(self.X, g_kd)])
+        out["noise"] = np.array([s * np.sum(g_lam)])
+        out["mean"] = -g_err.sum(0)
+        if with_Z:
+            out["Z"] = point_grads(self.spec, self.Z, None, Guu) + point_grads(self.spec, self.Z, self.X, Guf)
+        return {k: -g for k, g in out.items()}
+
+    def predict_f(self, xs, diag=True):
+        """the collapsed equations of _fitc.py _predict (+ the constant mean)."""
+        xs = xr.ld(xs)
+        t1 = xr.solve_lower(self.L, xr.expr_K(self.spec, self.Z, xs))
+        t2 = xr.solve_lower(self.LB, t1)
+        mean = t2.T @ self.c + self.mean
+        if diag:
+            return mean, np.repeat((xr.expr_Kdiag(self.spec, xs) - np.sum(t1 * t1, 0) + np.sum(t2 * t2, 0))[:, None], self.p, 1)
+        return mean, xr.expr_K(self.spec, xs, None) + t2.T @ t2 - t1.T @ t1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the plain fp64 evaluations behind e64
 # ---------------------------------------------------------------------------------------------------------------------
 def _t(a):
@@ -405,6 +515,34 @@ class Direct64VFE(xr.DirectVFE):
             return mean.numpy(), (self.K(xs) + t2.t() @ t2 - t1.t() @ t1).numpy()
 
 
+class Direct64FITC(Direct64VFE):
+    """the M-sized (Woodbury) fp64 evaluation of FITC (tests/_fitc_oracle.FITCOracle.woodbury_lml) with Direct64VFE's leaves and
+    its K by direct differences; gradients by autograd (Direct64VFE.loss_and_grads)."""
+
+    def _inputs(self):
+        return self.K(self.Z), self.K(self.Z, self.X), _direct_Kdiag(self.spec, self.raw, self.X), self.noise, self.Y
+
+    def log_likelihood(self):
+        return fo.FITCOracle.woodbury_lml(*self._inputs()).reshape(())
+
+    def predict_f(self, x_new, diag=True):
+        with torch.no_grad():
+            xs = _t(x_new)
+            Kuu, Kuf, Kd, s2, err = self._inputs()
+            L = torch.linalg.cholesky(Kuu)
+            A = orc.trtrs(Kuf, L)
+            lam = Kd - A.pow(2).sum(0) + s2
+            LB = torch.linalg.cholesky(torch.eye(Kuu.shape[0], dtype=torch.float64) + (A / lam) @ A.t())
+            c = orc.trtrs((A / lam) @ err, LB)
+            t1 = orc.trtrs(self.K(self.Z, xs), L)
+            t2 = orc.trtrs(t1, LB)
+            mean = t2.t() @ c + self.mean_val
+            if diag:
+                v = _direct_Kdiag(self.spec, self.raw, xs) - t1.pow(2).sum(0) + t2.pow(2).sum(0)
+                return mean.numpy(), v[:, None].expand_as(mean).numpy()
+            return mean.numpy(), (self.K(xs) + t2.t() @ t2 - t1.t() @ t1).numpy()
+
+
 class Direct64SVGP(so.SVGPOracle):
     """tests/_svgp_oracle.SVGPOracle with its K by direct differences: only the arithmetic differs from SVGPRef."""
 
@@ -479,6 +617,37 @@ VFE_CASES = [
     dict(name="ladder", n=400, m=40, d=2, dy=1, kernel=dict(kind="Rbf", variance=1.1, length_scales=0.8), noise=0.05, seed=411, knobs=[{}],
          ladder=True),
 ]
+# FITC: kernel hyper-parameters, noise and seeds of the VFE rows of the same name (new seeds where there is none); `mean`: a
+# Constant mean function.  inverse_knob_ignored: a hooked evaluation never takes the inverse form, whatever INVERSE_MIN_M says.
+FITC_CASES = [
+    dict(name="one_chunk", n=300, m=40, d=1, dy=1, kernel=dict(kind="Exp", variance=1.1, length_scales=0.6), noise=0.05, seed=301, knobs=[{}]),
+    dict(name="m_odd_across_a_leaf", n=700, m=129, d=3, dy=2, kernel=dict(kind="Matern52", variance=1.2, length_scales=[0.8, 1.0, 1.2], ARD=True),
+         noise=0.05, mean=[0.3, -0.2], seed=601, knobs=[{}]),
+    dict(name="dy_across_16", n=200, m=33, d=2, dy=17, kernel=dict(kind="Matern32", variance=1.3, length_scales=0.8), noise=0.05,
+         mean=[0.3, -0.2, 0.1, 0.0, 0.25, -0.4, 0.15, 0.05, -0.1, 0.2, -0.3, 0.35, -0.15, 0.45, -0.05, 0.4, -0.25], seed=611, knobs=[{}]),
+    dict(name="ragged_multi_chunk", n=1300, m=130, d=3, dy=5, kernel=dict(kind="Rbf", variance=1.1, length_scales=[0.5, 0.6, 0.7], ARD=True),
+         noise=0.1, seed=321, knobs=[dict(CHUNK_ROWS=256, LANES=1), dict(CHUNK_ROWS=256, LANES=2)], chunks=[256] * 5 + [20]),
+    dict(name="exact_multiple", n=1024, m=64, d=2, dy=1, kernel=dict(kind="Matern32", variance=1.3, length_scales=0.8), noise=0.05, seed=331,
+         knobs=[dict(CHUNK_ROWS=256)], chunks=[256] * 4),
+    dict(name="short_k_slices", n=1300, m=130, d=3, dy=1, kernel=_M52, noise=0.05, seed=341,
+         knobs=[dict(CHUNK_ROWS=512, SYRK_K_SLICE=128), dict(CHUNK_ROWS=512, SYRK_K_SLICE=0)], chunks=[512, 512, 276]),
+    dict(name="split_k_tail", n=8592, m=130, d=3, dy=2, kernel=dict(kind="Matern32", variance=1.3, length_scales=0.9), noise=0.05, seed=351,
+         knobs=[dict(CHUNK_ROWS=8192, SPLIT_K=2)], chunks=[8192, 400]),
+    dict(name="split_k_miss", n=8200, m=130, d=3, dy=1, kernel=_M52, noise=0.05, seed=361,
+         knobs=[dict(CHUNK_ROWS=8320, SPLIT_K=2), dict(CHUNK_ROWS=8192, SPLIT_K=2)]),
+    dict(name="blocked_one_block", n=700, m=130, d=3, dy=2, kernel=_M52, noise=0.05, seed=381,
+         knobs=[dict(BLOCKED_SOLVE_MIN_M=128, CHUNK_ROWS=256)], chunks=[256, 256, 188]),
+    dict(name="blocked_two_blocks", n=4700, m=1153, d=3, dy=1, kernel=dict(kind="Matern52", variance=1.2, length_scales=0.7), noise=0.05, seed=391,
+         knobs=[dict(BLOCKED_SOLVE_MIN_M=1024, CHUNK_ROWS=2048)], chunks=[2048, 2048, 604], golden=True),
+    dict(name="composite", n=500, m=48, d=3, dy=1, kernel=_COMP, noise=0.08, seed=401,
+         knobs=[dict(CHUNK_ROWS=256, LANES=1), dict(CHUNK_ROWS=256, LANES=2)], chunks=[256, 244]),
+    # (cond K(Z) ~ 1e8, as VFE's inverse_form: the one case besides the ladder whose tolerances stand above the floors.  Seeds 621,
+    # 631 and 641 put d/dZ's e64 at 5e-9 and more, 16 e64 at or over the host tests' cap of 1e-7; 651 leaves it 2.8x under)
+    dict(name="inverse_knob_ignored", n=600, m=130, d=2, dy=1, kernel=dict(kind="Rbf", variance=1.1, length_scales=0.35), noise=0.1, seed=651,
+         knobs=[dict(INVERSE_MIN_M=128, CHUNK_ROWS=256)], chunks=[256, 256, 88]),
+    dict(name="ladder", n=400, m=40, d=2, dy=1, kernel=dict(kind="Rbf", variance=1.1, length_scales=0.8), noise=0.05, seed=411, knobs=[{}],
+         ladder=True),
+]
 SVGP_CASES = [
     dict(name="small", n=37, m=5, d=1, dy=1, kernel=dict(kind="Exp", variance=1.1, length_scales=0.6), noise=0.1, seed=501, knobs=[{}]),
     dict(name="dy9", n=130, m=40, d=3, dy=9, kernel=dict(kind="Matern52", variance=1.2, length_scales=[0.8, 1.0, 1.2], ARD=True), noise=0.05,
@@ -519,6 +688,16 @@ def svgp_refs(case, inp, **plant):
                     num_data=case["n"], **plant),
             Direct64SVGP(inp["x"], inp["y"], inp["z"], case["kernel"], noise=case["noise"], q_mu=inp["q_mu"], q_sqrt=inp["q_sqrt"],
                          mean=case.get("mean")))
+
+
+def fitc_refs(case, inp, jitter=0.0, **plant):
+    return (FITCRef(inp["x"], inp["y"], inp["z"], case["kernel"], case["noise"], mean=case.get("mean"), jitter=jitter, **plant),
+            Direct64FITC(inp["x"], inp["y"], inp["z"], case["kernel"], case["noise"], mean=case.get("mean"), jitter=jitter))
+
+
+def fitc_reference(case, inp, jitter=0.0):
+    ref, d64 = fitc_refs(case, inp, jitter)
+    return evaluate(ref, d64, inp["xs"], with_Z=True)
 
 
 def vfe_reference(case, inp, jitter=0.0):
