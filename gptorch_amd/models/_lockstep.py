@@ -329,9 +329,26 @@ def _laplace_key(m):
     return SiteKey("laplace", k._kind, m._lik_kind, tuple(m.X.shape), int(k.length_scales.numel()), m.X.device)
 
 
-def _site_groups(models, cls, lockstep, key_of, per_model):
-    """[(key, indices)] of the cls (LaplaceGP / EPGP) models that can share one lock-step evaluation: the class's own log_likelihood
-    over points on the GPU, of a size lockstep.supported() admits, by key_of, in chunks that fit the device's free memory"""
+def _ep_key(m):
+    k = m.kernel
+    link = m._lik_kind
+    # (probit's moments are closed form: its models share a group whatever their likelihood's quadrature setting)
+    H = 0 if link == _native.LIK_PROBIT else int(m.likelihood.num_gauss_hermite_points)
+    return SiteKey("ep", k._kind, link, tuple(m.X.shape), int(k.length_scales.numel()), m.X.device, H)
+
+
+def _family_module(tag):
+    """the lock-step module of a SiteKey's family; each gives MODEL, supported, per_model_bytes, search and its node"""
+    from . import _ep_lockstep, _laplace_lockstep
+    return {"laplace": _laplace_lockstep, "ep": _ep_lockstep}[tag]
+
+
+def _site_groups(models, tag, key_of):
+    """[(SiteKey, indices)] of the family's (LaplaceGP / EPGP) models that can share one lock-step evaluation: the class's own
+    log_likelihood over points on the GPU, of a size the family's supported() admits, by key_of, in chunks that fit the device's free
+    memory"""
+    lockstep = _family_module(tag)
+    cls = lockstep.MODEL
     groups = {}
     for i, m in enumerate(models):
         if not isinstance(m, cls) or type(m).log_likelihood is not cls.log_likelihood:
@@ -339,17 +356,20 @@ def _site_groups(models, cls, lockstep, key_of, per_model):
         if not (isinstance(m.X, torch.Tensor) and m.X.is_cuda) or not lockstep.supported(m.X.shape[0]):
             continue
         groups.setdefault(key_of(m), []).append(i)
-    return _chunked(groups, per_model)
+    return _chunked(groups, lambda key: lockstep.per_model_bytes(key.shape[0], key.nls))
 
 
 def _laplace_groups(models):
     """[(SiteKey, indices)]: _site_groups of the LaplaceGP models (_laplace_lockstep.BatchedLaplaceEvidence)"""
-    from . import _laplace_lockstep
-    from .laplace import LaplaceGP
-    return _site_groups(models, LaplaceGP, _laplace_lockstep, _laplace_key, lambda key: _laplace_lockstep.per_model_bytes(key.shape[0]))
+    return _site_groups(models, "laplace", _laplace_key)
 
 
-def _laplace_group_inputs(ms, differentiable):
+def _ep_groups(models):
+    """[(SiteKey, indices)]: _site_groups of the EPGP models (_ep_lockstep.BatchedEPEvidence)"""
+    return _site_groups(models, "ep", _ep_key)
+
+
+def _site_group_inputs(ms, differentiable):
     """(X, Y, variance [B], length scales [B, nls], [m_b = mean_function(X_b)]) of one _laplace_groups / _ep_groups group"""
     X, Y = _shared_or_stacked(ms)
     var = _stacked([m.kernel.variance for m in ms], differentiable).reshape(len(ms))
@@ -359,35 +379,14 @@ def _laplace_group_inputs(ms, differentiable):
     return X, Y, var, ls, means
 
 
-def _group_evidence(node, ms, key, differentiable):
-    """the lock-step evidences [B] of one LaplaceGP / EPGP group by its node (autograd-connected when differentiable)"""
-    X, Y, var, ls, means = _laplace_group_inputs(ms, differentiable)
-    return node.apply(X, Y, var, ls, key.kind, key.lik_kind, ms, _batch_holder((key, len(ms))), *means)
+def _site_group_evidence(ms, group, differentiable):
+    """the lock-step evidences [B] of one LaplaceGP / EPGP group by its family's node (autograd-connected when differentiable)"""
+    key = group.key
+    X, Y, var, ls, means = _site_group_inputs(ms, differentiable)
+    return _family_module(key.tag).NODE.apply(X, Y, var, ls, key.kind, key.lik_kind, ms, _batch_holder((key, len(ms))), *means)
 
 
-def _laplace_group_evidence(ms, group, differentiable):
-    from . import _laplace_lockstep
-    return _group_evidence(_laplace_lockstep.BatchedLaplaceEvidence, ms, group.key, differentiable)
-
-
-def _ep_key(m):
-    k = m.kernel
-    link = m._lik_kind
-    # (probit's moments are closed form: its models share a group whatever their likelihood's quadrature setting)
-    H = 0 if link == _native.LIK_PROBIT else int(m.likelihood.num_gauss_hermite_points)
-    return SiteKey("ep", k._kind, link, tuple(m.X.shape), int(k.length_scales.numel()), m.X.device, H)
-
-
-def _ep_groups(models):
-    """[(SiteKey, indices)]: _site_groups of the EPGP models (_ep_lockstep.BatchedEPEvidence)"""
-    from . import _ep_lockstep
-    from .ep import EPGP
-    return _site_groups(models, EPGP, _ep_lockstep, _ep_key, lambda key: _ep_lockstep.per_model_bytes(key.shape[0], key.nls))
-
-
-def _ep_group_evidence(ms, group, differentiable):
-    from . import _ep_lockstep
-    return _group_evidence(_ep_lockstep.BatchedEPEvidence, ms, group.key, differentiable)
+_laplace_group_evidence = _ep_group_evidence = _site_group_evidence       # (the names each family's tests and tools call it by)
 
 
 def _group_data(ms, differentiable=False, key=None):
@@ -473,32 +472,19 @@ def _expr_value(ms, group, differentiable):
     return lml if differentiable else [lml[b:b + 1].clone() for b in range(len(ms))]       # (rows: every model its own copy)
 
 
-def _laplace_search(ms, key, X, Y, mu, var, ls, starts):
-    from . import _laplace_lockstep
-    return _laplace_lockstep.find_modes(key.kind, key.lik_kind, X, Y, mu, var, ls, starts, [m.newton_tol for m in ms], [m.max_newton_iter for m in ms])
-
-
-def _ep_search(ms, key, X, Y, mu, var, ls, starts):
-    from . import _ep_lockstep
-    return _ep_lockstep.find_sites_batched(key.kind, key.lik_kind, X, Y, mu, var, ls, ms[0]._rule(X.device), starts,
-                                           [m.ep_tol for m in ms], [m.max_sweeps for m in ms], [m.damping for m in ms])
-
-
-def _search_seed(search):
+def _site_seed(ms, group):
     """LaplaceGP / EPGP folds: the searches (mode / sites) in lock step into buffers of their own; every model's prediction cache
     gets its state, with a in the factor's extra row as the class's _mode_for_predict leaves it"""
-    def seed(ms, group):
-        key = group.key
-        X, Y, var, ls, means = _laplace_group_inputs(ms, differentiable=False)
-        n = X.shape[-2]
-        states = search(ms, key, X, Y.reshape(n) if Y.dim() == 2 else Y.reshape(len(ms), n),
-                        torch.stack([mu.reshape(n) for mu in means]), var, ls, [m._start(n) for m in ms])
-        for m, state in zip(ms, states):
-            m._remember(state)
-            state.factor.A[n, :n] = state.a
-            m._seed_cached_state((key.tag, key.kind), m.X, state)
-        return len(ms)
-    return seed
+    key = group.key
+    X, Y, var, ls, means = _site_group_inputs(ms, differentiable=False)
+    n = X.shape[-2]
+    stack = _family_module(key.tag).search(ms, key.kind, key.lik_kind, X, Y.reshape(n) if Y.dim() == 2 else Y.reshape(len(ms), n),
+                                           torch.stack([mu.reshape(n) for mu in means]), var, ls, [m._start(n) for m in ms])
+    for m, state in zip(ms, stack.states):
+        m._remember(state)
+        state.factor.A[n, :n] = state.a
+        m._seed_cached_state((key.tag, key.kind), m.X, state)
+    return len(ms)
 
 
 # Every kind of lock-step group, in the order in which the entry points evaluate them (it fixes the LRU order of _BATCH_BUFFERS
@@ -510,8 +496,8 @@ FAMILIES = (
     Family("expr", _expression_groups, _expr_value, True),
     Family("vfe", _vfe_groups, _vfe_group_bound, False),
     # (capture=True: LaplaceGP and EPGP models keep their own optimize())
-    Family("laplace", _laplace_groups, _laplace_group_evidence, True, seed=_search_seed(_laplace_search), captured=False),
-    Family("ep", _ep_groups, _ep_group_evidence, True, seed=_search_seed(_ep_search), captured=False),
+    Family("laplace", _laplace_groups, _site_group_evidence, True, seed=_site_seed, captured=False),
+    Family("ep", _ep_groups, _site_group_evidence, True, seed=_site_seed, captured=False),
 )
 _HELD_BESIDE_FB = tuple(name for family in FAMILIES for name in family.held)
 

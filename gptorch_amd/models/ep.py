@@ -37,7 +37,7 @@ Gradients at the fixed point (R&W eq. 5.27: no implicit term), with R = diag(s) 
 
 Likelihoods: Bernoulli("probit") (closed-form moments, R&W eqs. 3.58 and 3.82) and Bernoulli("logit") (the three moments by the
 likelihood's own Gauss-Hermite rule of num_gauss_hermite_points nodes: that rule is the model's definition, as it is for
-propagate_log).  Prediction is LaplaceGP._predict over (a, s, the factor) of the converged sites.
+propagate_log).  Prediction is LaplaceGP's (laplace.SearchedGP._predict) over (a, s, the factor) of the converged sites.
 
 Lock step: equal-shape EPGP models handed to multi_start_optimize / batched_log_likelihood / batched_loss_and_grad /
 batched_factorise run their searches, evidences and gradients as one group (models/_ep_lockstep.py, _lockstep._ep_groups), every
@@ -51,8 +51,8 @@ import torch
 
 from .. import _backward, _ops, kernels, likelihoods
 from .._native import LIK_LOGIT, LIK_PROBIT, NativeError
-from .base import GPModel
-from .laplace import LaplaceGP, W_FLOOR, _dot, _factor_system
+from ._site_lockstep import Evidence
+from .laplace import SearchedGP, SearchEvidence, W_FLOOR, _dot, _factor_system, _inverse_at
 
 STALL_BELOW = 1e-6         # a change that no longer decreases counts as a stall only below this fraction of the sites' scale
 
@@ -120,53 +120,26 @@ def find_sites(kind, lik_kind, X, y, m, var, ls, rule=(None, None), sites0=None,
 
 
 def _evidence_gradients(kind, X, var, ls, st):
-    """the closed form of the module docstring at one search's sites -> g [1 + nls] = dlog Z_EP/d(variance, length_scales)"""
-    f = st.factor
-    if f.generation != st.generation:
-        # the model's reusable buffer was refactorised by a later forward: rebuild this node's factor privately
-        f = _ops.Factor(f.n, 1, f.device)
-        _factor_system(kind, X, var, ls, st.s, f)
-    Binv = _backward._kinv_lower(f, _backward._upper_inverse(f))
+    """the closed form of the module docstring at one search's sites -> (g [1 + nls] = dlog Z_EP/d(variance, length_scales), None:
+    there is no u)"""
+    _, Binv = _inverse_at(kind, X, var, ls, st)
     zero = torch.zeros_like(st.a)
-    return _ops.laplace_grad(kind, X, var, ls, st.s, Binv, st.a, zero, zero)
+    return _ops.laplace_grad(kind, X, var, ls, st.s, Binv, st.a, zero, zero), None
 
 
-class EPEvidence(torch.autograd.Function):
-    """log Z_EP as ONE autograd node: the EP search in the forward, the closed form of the module docstring in the backward.
-    Inputs: the points, the targets [n, 1], m = mean_function(X) [n, 1], the CONSTRAINED variance and length-scales; gradients
-    for m, variance and length-scales."""
-
-    @staticmethod
-    def forward(ctx, X, Y, m, variance, length_scales, kind, lik_kind, owner):
-        y, mv = Y.detach().reshape(-1), m.detach().reshape(-1)
-        st = find_sites(kind, lik_kind, X, y, mv, variance.detach(), length_scales.detach(), rule=owner._rule(X.device),
-                        sites0=owner._start(X.shape[0]), factor=owner._holder.get("factor"), ep_tol=owner.ep_tol,
-                        max_sweeps=owner.max_sweeps, damping=owner.damping)
-        owner._holder["factor"] = st.factor
-        owner._remember(st)
-        ctx.kind, ctx.st = kind, st
-        ctx.save_for_backward(X, variance, length_scales)
-        return st.evidence.reshape(1)
-
-    @staticmethod
-    def backward(ctx, grad_out):
-        X, variance, length_scales = ctx.saved_tensors
-        kind, st = ctx.kind, ctx.st
-        n = st.factor.n
-        g = _evidence_gradients(kind, X, variance.detach(), length_scales.detach(), st)
-        go = grad_out.reshape(())
-        nls = length_scales.numel()
-        return (None, None, (go * st.a).reshape(n, 1) if ctx.needs_input_grad[2] else None,
-                (go * g[0:1]).reshape(variance.shape), (go * g[1:1 + nls]).reshape(length_scales.shape), None, None, None)
+class EPEvidence(SearchEvidence):
+    """log Z_EP: the EP search in the forward, the closed form of the module docstring in the backward"""
+    family = Evidence(value=lambda st: st.evidence, gradients=_evidence_gradients, mean_gradient=lambda st, _u: st.a)
 
 
-class EPGP(GPModel):
+class EPGP(SearchedGP):
     """EPGP(x, y, kernel, likelihood): the exact GP under Bernoulli("probit" | "logit") labels, its hyper-parameters fitted on
     the evidence of expectation propagation (see the module docstring).  GPU only.
 
     ep_tol, max_sweeps, damping: the stopping rule and the step of the parallel sweeps.  warm_start (default on): a search starts
     at the previous evaluation's sites when the shapes match; reset_sites() drops them.  ep_stats: {"sweeps", "stalled"} of the
     last search."""
+    _tag = "ep"
 
     def __init__(self, x, y, kernel, likelihood, mean_function=None, name="ep_gp"):
         if not (isinstance(kernel, kernels.Stationary) and kernel._kind is not None):
@@ -207,6 +180,10 @@ class EPGP(GPModel):
             return (None, None)
         return likelihoods.gauss_hermite(self.likelihood.num_gauss_hermite_points, device)
 
+    def _search(self, kind, lik_kind, X, y, m, var, ls, factor=None):
+        return find_sites(kind, lik_kind, X, y, m, var, ls, rule=self._rule(X.device), sites0=self._start(X.shape[0]), factor=factor,
+                          ep_tol=self.ep_tol, max_sweeps=self.max_sweeps, damping=self.damping)
+
     def _remember(self, st):
         self._sites = (st.tau, st.nu)
         self.ep_stats = {"sweeps": st.sweeps, "stalled": st.stalled}
@@ -220,23 +197,3 @@ class EPGP(GPModel):
         k = self.kernel
         return EPEvidence.apply(x, y, self.mean_function(x), k.variance.transform(), k.length_scales.transform(), k._kind,
                                 self._lik_kind, self)
-
-    def _mode_for_predict(self, x):
-        """the state LaplaceGP._predict starts from: (a, s, the factor) of the converged sites, a in the factor's extra row."""
-        k = self.kernel
-        with torch.no_grad():
-            var, ls = k.variance.transform(), k.length_scales.transform()
-
-            def build():
-                st = find_sites(k._kind, self._lik_kind, x, self.Y.reshape(-1), self.mean_function(x).reshape(-1), var, ls,
-                                rule=self._rule(x.device), sites0=self._start(x.shape[0]), ep_tol=self.ep_tol,
-                                max_sweeps=self.max_sweeps, damping=self.damping)
-                self._remember(st)
-                st.factor.A[st.factor.n, :st.factor.n] = st.a
-                return st
-
-            st = self._cached_state(("ep", k._kind), x, build)
-            self._predict_calls += 1
-        return st, var, ls
-
-    _predict = LaplaceGP._predict          # q(f* | y) from (a, s, factor): the state provider above is all that differs

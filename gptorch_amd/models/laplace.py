@@ -49,6 +49,7 @@ import torch
 
 from .. import _backward, _ops, kernels, likelihoods
 from .._native import LIK_LOGIT, LIK_POISSON, LIK_PROBIT, NativeError
+from ._site_lockstep import Evidence
 from .base import GPModel
 
 MAX_HALVINGS = 10
@@ -147,57 +148,110 @@ def _solve_b(factor, w):
     return _ops.backsub(factor)[0]
 
 
-def _evidence_gradients(kind, X, var, ls, mode):
-    """the closed form of the module docstring at one mode -> (g [1 + nls] = dlog q/d(variance, length_scales), u [n])"""
-    f = mode.factor
-    if f.generation != mode.generation:
+def _inverse_at(kind, X, var, ls, state):
+    """(the factor of B at a search's state, B^-1 from it)"""
+    f = state.factor
+    if f.generation != state.generation:
         # the model's reusable buffer was refactorised by a later forward: rebuild this node's factor privately
         f = _ops.Factor(f.n, 1, f.device)
-        _factor_system(kind, X, var, ls, mode.s, f)
-    Binv = _backward._kinv_lower(f, _backward._upper_inverse(f))
+        _factor_system(kind, X, var, ls, state.s, f)
+    return f, _backward._kinv_lower(f, _backward._upper_inverse(f))
+
+
+def _evidence_gradients(kind, X, var, ls, mode):
+    """the closed form of the module docstring at one mode -> (g [1 + nls] = dlog q/d(variance, length_scales), u [n])"""
+    f, Binv = _inverse_at(kind, X, var, ls, mode)
     sigma = _ops.laplace_diag(kind, X, var, ls, mode.s, Binv)
     s2 = 0.5 * sigma * mode.d3
     u = s2 - mode.s * _solve_b(f, mode.s * _ops.laplace_matvec(kind, X, var, ls, s2))
     return _ops.laplace_grad(kind, X, var, ls, mode.s, Binv, mode.a, u, mode.d1), u
 
 
-class LaplaceEvidence(torch.autograd.Function):
-    """log q(y | theta) as ONE autograd node: the Newton loop in the forward, the closed form of the module docstring in the
-    backward.  Inputs: the points, the targets [n, 1], m = mean_function(X) [n, 1], the CONSTRAINED variance and
-    length-scales; gradients for m, variance and length-scales."""
+class SearchEvidence(torch.autograd.Function):
+    """one model's approximate evidence as ONE autograd node: the owner's search in the forward, the family's closed form in the
+    backward; a family's node is a subclass that sets `family` (a _site_lockstep.Evidence; forward and backward, static methods,
+    find it through ctx._forward_cls: the class whose apply() was called, which torch.autograd sets on every node's class).  Inputs: the points, the targets [n, 1],
+    m = mean_function(X) [n, 1], the CONSTRAINED variance and length-scales, the kernel and likelihood kinds, the model; gradients
+    for m, variance and length-scales."""
+    family = None
 
     @staticmethod
     def forward(ctx, X, Y, m, variance, length_scales, kind, lik_kind, owner):
-        y, mv = Y.detach().reshape(-1), m.detach().reshape(-1)
-        var, ls = variance.detach(), length_scales.detach()
-        mode = find_mode(kind, lik_kind, X, y, mv, var, ls, a0=owner._start(X.shape[0]), factor=owner._holder.get("factor"),
-                         newton_tol=owner.newton_tol, max_newton_iter=owner.max_newton_iter)
-        owner._holder["factor"] = mode.factor
-        owner._remember(mode)
-        ctx.kind, ctx.mode = kind, mode
+        state = owner._search(kind, lik_kind, X, Y.detach().reshape(-1), m.detach().reshape(-1), variance.detach(), length_scales.detach(),
+                              factor=owner._holder.get("factor"))
+        owner._holder["factor"] = state.factor
+        owner._remember(state)
+        ctx.kind, ctx.state = kind, state
         ctx.save_for_backward(X, variance, length_scales)
-        return (mode.value - 0.5 * _dot(mode.a, mode.Ka) - mode.sum_log_diag).reshape(1)
+        return ctx._forward_cls.family.value(state).reshape(1)
 
     @staticmethod
     def backward(ctx, grad_out):
+        family = ctx._forward_cls.family
         X, variance, length_scales = ctx.saved_tensors
-        kind, mode = ctx.kind, ctx.mode
-        var, ls = variance.detach(), length_scales.detach()
-        n = mode.factor.n
-        g, u = _evidence_gradients(kind, X, var, ls, mode)
+        kind, state = ctx.kind, ctx.state
+        n = state.factor.n
+        g, u = family.gradients(kind, X, variance.detach(), length_scales.detach(), state)
         go = grad_out.reshape(())
         nls = length_scales.numel()
-        return (None, None, (go * (mode.d1 + u)).reshape(n, 1) if ctx.needs_input_grad[2] else None,
+        return (None, None, (go * family.mean_gradient(state, u)).reshape(n, 1) if ctx.needs_input_grad[2] else None,
                 (go * g[0:1]).reshape(variance.shape), (go * g[1:1 + nls]).reshape(length_scales.shape), None, None, None)
 
 
-class LaplaceGP(GPModel):
+class LaplaceEvidence(SearchEvidence):
+    """log q(y | theta): the Newton loop in the forward, the closed form of the module docstring in the backward"""
+    family = Evidence(value=lambda mode: mode.value - 0.5 * _dot(mode.a, mode.Ka) - mode.sum_log_diag, gradients=_evidence_gradients,
+                      mean_gradient=lambda mode, u: mode.d1 + u)
+
+
+class SearchedGP(GPModel):
+    """what LaplaceGP and EPGP (models/ep.py) share: q(f* | y) from what a search leaves -- a, s and the factor of
+    B = I + diag(s) K diag(s).  A subclass gives _tag (it names the cached state), _search, _start and _remember."""
+
+    def _mode_for_predict(self, x):
+        """the state _predict starts from, a in the factor's extra row: the operand of the predictive mean"""
+        k = self.kernel
+        with torch.no_grad():
+            var, ls = k.variance.transform(), k.length_scales.transform()
+
+            def build():
+                state = self._search(k._kind, self._lik_kind, x, self.Y.reshape(-1), self.mean_function(x).reshape(-1), var, ls)
+                self._remember(state)
+                state.factor.A[state.factor.n, :state.factor.n] = state.a
+                return state
+
+            state = self._cached_state((self._tag, k._kind), x, build)
+            self._predict_calls += 1
+        return state, var, ls
+
+    def _predict(self, x_new, diag=True, x=None):
+        """q(f* | y): mean [n*, 1]; var [n*, 1] (diag) or cov [n*, n*]."""
+        x = x if x is not None else self.X
+        mode, var, ls = self._mode_for_predict(x)
+        k, f = self.kernel, mode.factor
+        n, ns = f.n, x_new.shape[0]
+        with torch.no_grad():
+            Bt = _ops.padded_like_factor(f, ns)
+            _ops.kernel_matrix(k._kind, x_new, x, var, ls, out=Bt, ldk=f.ld)                  # K(x*, X)
+            kpad = _ops.round_up(n, 16)
+            mean = _ops.gemm_nt(Bt, f.A[n:], ns, 1, kpad) + self.mean_function(x_new)        # K(x*, X) a^ + m(x*)
+            Bt[:ns, :n] *= mode.s                                                            # K(x*, X) diag(s)
+            f.solve_right_lt(Bt, ns)                                                         # V^T = K(x*, X) diag(s) L^-T
+            if diag:
+                return mean, (var.expand(ns) - _ops.row_sumsq(Bt, ns, n))[:, None]
+            cov = _ops.kernel_matrix(k._kind, x_new, None, var, ls)
+            _ops.gemm_nt(Bt, Bt, ns, ns, kpad, alpha=-1.0, beta=1.0, C=cov)
+            return mean, cov
+
+
+class LaplaceGP(SearchedGP):
     """LaplaceGP(x, y, kernel, likelihood): the exact GP under Bernoulli("probit" | "logit") labels or Poisson counts, its
     hyper-parameters fitted on Laplace's approximate evidence (see the module docstring).  GPU only.
 
     newton_tol, max_newton_iter: the stopping rule of the mode search.  warm_start (default on): a search starts at the
     previous evaluation's mode when the shapes match; reset_mode() drops it.  newton_stats: {"steps", "halvings"} of the
     last search."""
+    _tag = "laplace"
 
     def __init__(self, x, y, kernel, likelihood, mean_function=None, name="laplace_gp"):
         if not (isinstance(kernel, kernels.Stationary) and kernel._kind is not None):
@@ -235,6 +289,10 @@ class LaplaceGP(GPModel):
         a = self._mode_a
         return a if (self.warm_start and a is not None and a.numel() == n and a.device == self.X.device) else None
 
+    def _search(self, kind, lik_kind, X, y, m, var, ls, factor=None):
+        return find_mode(kind, lik_kind, X, y, m, var, ls, a0=self._start(X.shape[0]), factor=factor, newton_tol=self.newton_tol,
+                         max_newton_iter=self.max_newton_iter)
+
     def _remember(self, mode):
         self._mode_a = mode.a
         self.newton_stats = {"steps": mode.steps, "halvings": mode.halvings}
@@ -248,38 +306,3 @@ class LaplaceGP(GPModel):
         k = self.kernel
         return LaplaceEvidence.apply(x, y, self.mean_function(x), k.variance.transform(), k.length_scales.transform(), k._kind,
                                      self._lik_kind, self)
-
-    def _mode_for_predict(self, x):
-        k = self.kernel
-        with torch.no_grad():
-            var, ls = k.variance.transform(), k.length_scales.transform()
-
-            def build():
-                mode = find_mode(k._kind, self._lik_kind, x, self.Y.reshape(-1), self.mean_function(x).reshape(-1), var, ls,
-                                 a0=self._start(x.shape[0]), newton_tol=self.newton_tol, max_newton_iter=self.max_newton_iter)
-                self._remember(mode)
-                mode.factor.A[mode.factor.n, :mode.factor.n] = mode.a          # the extra row: the operand of the predictive mean
-                return mode
-
-            mode = self._cached_state(("laplace", k._kind), x, build)
-            self._predict_calls += 1
-        return mode, var, ls
-
-    def _predict(self, x_new, diag=True, x=None):
-        """q(f* | y): mean [n*, 1]; var [n*, 1] (diag) or cov [n*, n*]."""
-        x = x if x is not None else self.X
-        mode, var, ls = self._mode_for_predict(x)
-        k, f = self.kernel, mode.factor
-        n, ns = f.n, x_new.shape[0]
-        with torch.no_grad():
-            Bt = _ops.padded_like_factor(f, ns)
-            _ops.kernel_matrix(k._kind, x_new, x, var, ls, out=Bt, ldk=f.ld)                  # K(x*, X)
-            kpad = _ops.round_up(n, 16)
-            mean = _ops.gemm_nt(Bt, f.A[n:], ns, 1, kpad) + self.mean_function(x_new)        # K(x*, X) a^ + m(x*)
-            Bt[:ns, :n] *= mode.s                                                            # K(x*, X) diag(s)
-            f.solve_right_lt(Bt, ns)                                                         # V^T = K(x*, X) diag(s) L^-T
-            if diag:
-                return mean, (var.expand(ns) - _ops.row_sumsq(Bt, ns, n))[:, None]
-            cov = _ops.kernel_matrix(k._kind, x_new, None, var, ls)
-            _ops.gemm_nt(Bt, Bt, ns, ns, kpad, alpha=-1.0, beta=1.0, C=cov)
-            return mean, cov

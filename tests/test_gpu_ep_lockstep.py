@@ -217,6 +217,18 @@ def test_a_model_that_does_not_converge_falls_out(device):
     _assert_same_state(_lock_step(rest), rest, want, rest_alone)
 
 
+def test_a_replay_that_returns_is_a_disagreement(device, monkeypatch):
+    """a model that fails in the group is replayed alone to raise its own error; a replay that RETURNS (here: a stand-in for
+    find_sites) means the two searches disagree, and the call raises that -- nobody's state moved"""
+    lock = _restarts("probit_rbf_300x2", SETTINGS)
+    lock[1].max_sweeps = 1
+    monkeypatch.setattr(ep, "find_sites", lambda *args, **kwargs: object())
+    with pytest.raises(_native.NativeError, match="disagree") as got:
+        batched_loss_and_grad(lock)
+    assert "EPGP: model 1 " in str(got.value)
+    assert all(m._sites is None for m in lock)
+
+
 # ---- 6. batched_log_likelihood and batched_loss_and_grad -----------------------------------------------------------------------------------
 @pytest.mark.parametrize("with_mean", [False, True], ids=["zero_mean", "constant_mean_and_prior"])
 def test_batched_loss_and_grad(device, with_mean):

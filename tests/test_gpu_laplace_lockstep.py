@@ -313,6 +313,54 @@ def test_a_model_that_does_not_converge_falls_out(device):
     _assert_same_state(batched_loss_and_grad(rest), rest, want, rest_alone)
 
 
+def test_a_replay_that_returns_is_a_disagreement(device, monkeypatch):
+    """a model that fails in the group is replayed alone to raise its own error; a replay that RETURNS (here: a stand-in for
+    find_mode) means the two searches disagree, and the call raises that -- nobody's state moved"""
+    lock = _restarts("probit_rbf_300x2", [(0.3, 1.0), (1.7, 1.0), (8.0, 0.5)])
+    lock[1].max_newton_iter = 1
+    monkeypatch.setattr(laplace, "find_mode", lambda *args, **kwargs: object())
+    with pytest.raises(_native.NativeError, match="disagree") as got:
+        batched_loss_and_grad(lock)
+    assert "LaplaceGP: model 1 " in str(got.value)
+    assert all(m._mode_a is None for m in lock)
+
+
+def test_backward_survives_a_later_forward(device):
+    """the group's factor slots are reused by the next forward: an earlier node rebuilds its factors privately (the `generation`
+    check), and its gradients are those taken immediately"""
+    lock = _restarts("probit_rbf_300x2", [(0.3, 1.0), (1.7, 1.0), (8.0, 0.5)], mean=0.2)
+    (key, g), = _lockstep._laplace_groups(lock)
+    group = _lockstep.Group(None, key, g)
+
+    def forward():
+        for mdl in lock:
+            mdl.reset_mode()
+            mdl.zero_grad()
+        return -_lockstep._laplace_group_evidence(lock, group, differentiable=True)
+
+    def grads():
+        return [p.grad.clone() for mdl in lock for p in mdl.parameters() if p.grad is not None]
+    first = forward()
+    first.sum().backward()
+    want = grads()
+    assert len(want) == 9
+    first = forward()
+    with torch.no_grad():
+        for mdl in lock:
+            mdl.kernel.variance.data += 0.1
+    for mdl in lock:
+        mdl.reset_mode()
+    later = -_lockstep._laplace_group_evidence(lock, group, differentiable=True)  # refactorises the shared slots at other parameters
+    assert not torch.equal(later.detach(), first.detach())
+    with torch.no_grad():
+        for mdl in lock:
+            mdl.kernel.variance.data -= 0.1
+    factorised = ll.STATS["factorisations"]
+    first.sum().backward()
+    assert ll.STATS["factorisations"] == factorised + 3                   # the private rebuild happened
+    assert all(torch.equal(a, b) for a, b in zip(grads(), want))
+
+
 def test_mixed_list(device):
     """GPR + VFE + LaplaceGP groups and a singleton LaplaceGP of another N in one call"""
     def build():
