@@ -120,6 +120,11 @@ SIGNATURES = {
     "gpn_refine_finish": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "gpn_lik_expect": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p,
                                c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p]),
+    # likelihoods.MultiClass (csrc/multiclass.hip)
+    "gpn_lik_expect_robustmax": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_int,
+                                         c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p]),
+    "gpn_lik_robustmax_probs": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_double, c_void_p, c_void_p, c_int, c_void_p,
+                                        c_int64]),
     # LaplaceGP (csrc/laplace.hip; the back-substitution: csrc/refine.hip)
     "gpn_lik_derivs_work_bytes": (c_int64, [c_int64]),
     "gpn_lik_derivs": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -186,6 +191,7 @@ SIGNATURES = {
 }
 LIK_PROBIT, LIK_LOGIT, LIK_POISSON, LIK_STUDENT_T = 0, 1, 2, 3   # include/gpnative.h GPN_LIK_*
 LIK_ROWS_PER_GROUP = 256                                        # GPN_LIK_ROWS_PER_GROUP
+ROBUSTMAX_ROWS_PER_GROUP = 4                                    # GPN_ROBUSTMAX_ROWS_PER_GROUP
 class ExprTerm(ctypes.Structure):
     """include/gpnative.h gpn_expr_term: one leaf of a sum-of-products covariance expression."""
     _fields_ = [("type", c_int), ("kind", c_int), ("var_off", c_int), ("ls_off", c_int), ("nls", c_int), ("nvar", c_int)]

@@ -640,6 +640,49 @@ def lik_expect(kind, params, f_mean, f_var, y, nodes, weights, want_value=True, 
     return value, g_mean, g_var, g_params
 
 
+def _robustmax_operands(f_mean, f_var, nodes, weights):
+    if f_mean.dim() != 2 or f_mean.shape[1] < 2 or f_var.shape != (f_mean.shape[0],):
+        raise ValueError("expect f_mean [rows, C >= 2] and f_var [rows]; got %s, %s" % (tuple(f_mean.shape), tuple(f_var.shape)))
+    if nodes.shape != weights.shape or nodes.dim() != 1:
+        raise ValueError("expect nodes [H] and weights [H]; got %s, %s" % (tuple(nodes.shape), tuple(weights.shape)))
+    return (f_mean if f_mean.stride(1) == 1 else f_mean.contiguous()), _c(f_var), _c(nodes), _c(weights)
+
+
+def lik_expect_robustmax(f_mean, f_var, labels, eps, nodes, weights, want_value=True, want_mean=True, want_var=True):
+    """gpn_lik_expect_robustmax: the expected log-likelihood of the robust-max multi-class likelihood under N(f_mean[:, c], f_var)
+    (one variance per row) summed over the rows, with its gradients -> (value 0-dim, g_mean [rows, C], g_var [rows]); an output
+    that is not wanted is None.  labels [rows]: doubles holding the class indices.  ONE call, no host synchronisation."""
+    _req(f_mean, f_var, labels, nodes, weights)
+    f_mean, f_var, nodes, weights = _robustmax_operands(f_mean, f_var, nodes, weights)
+    rows, C = f_mean.shape
+    if labels.shape != (rows,):
+        raise ValueError("expect labels [%d]; got %s" % (rows, tuple(labels.shape)))
+    labels = _c(labels)
+    dev = f_mean.device
+    g = _native.ROBUSTMAX_ROWS_PER_GROUP
+    work = torch.empty((rows + g - 1) // g, dtype=torch.float64, device=dev)
+    value = torch.empty((), dtype=torch.float64, device=dev) if want_value else None
+    g_mean = torch.empty(rows, C, dtype=torch.float64, device=dev) if want_mean else None
+    g_var = torch.empty(rows, dtype=torch.float64, device=dev) if want_var else None
+    st = _native.lib().gpn_lik_expect_robustmax(_stream(dev), _ptr(f_mean), f_mean.stride(0), _ptr(f_var), _ptr(labels), rows, C, float(eps),
+                                                _ptr(nodes), _ptr(weights), nodes.numel(), _ptr(work), work.numel() * 8, _ptr(value),
+                                                _ptr(g_mean), C, _ptr(g_var))
+    _native.check(st, "gpn_lik_expect_robustmax")
+    return value, g_mean, g_var
+
+
+def lik_robustmax_probs(f_mean, f_var, eps, nodes, weights):
+    """gpn_lik_robustmax_probs -> p(y = c) [rows, C] of the robust-max likelihood under N(f_mean[:, c], f_var)."""
+    _req(f_mean, f_var, nodes, weights)
+    f_mean, f_var, nodes, weights = _robustmax_operands(f_mean, f_var, nodes, weights)
+    rows, C = f_mean.shape
+    probs = torch.empty(rows, C, dtype=torch.float64, device=f_mean.device)
+    st = _native.lib().gpn_lik_robustmax_probs(_stream(f_mean.device), _ptr(f_mean), f_mean.stride(0), _ptr(f_var), rows, C, float(eps),
+                                               _ptr(nodes), _ptr(weights), nodes.numel(), _ptr(probs), C)
+    _native.check(st, "gpn_lik_robustmax_probs")
+    return probs
+
+
 # ----------------------------------------------------------------------------
 # LaplaceGP (models/laplace.py): csrc/laplace.hip + the back-substitution of csrc/refine.hip
 # ----------------------------------------------------------------------------

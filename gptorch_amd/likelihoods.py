@@ -10,6 +10,11 @@ Everything in this file is plain torch (CPU or GPU, differentiable by autograd).
 the four new classes with ONE fused kernel instead (csrc/lik.hip through models/sparse_gpr.py, NATIVE_EXPECTATION): the same
 rule and its exact derivatives.  Bernoulli and Poisson also state logp_derivatives (logp and its first three derivatives in f):
 what models.LaplaceGP's Newton search needs, evaluated on the GPU by csrc/laplace.hip with the same closed forms.
+
+MultiClass (the robust-max likelihood over num_classes latent functions) COUPLES the latent columns of a row: it declares
+num_latent, SVGP then carries that many columns over one column of labels, and its expectation and predictive probabilities are
+variational_expectation / predict_mean_variance over all columns of a row at once -- plain torch here as well, and on the GPU one
+fused launch each (csrc/multiclass.hip, under the same NATIVE_EXPECTATION switch).
 """
 import math
 
@@ -212,6 +217,107 @@ class Bernoulli(_NonGaussian):
             f, w = self._quadrature(mean_f, var_f.expand_as(mean_f))
             p = (torch.sigmoid(f) * w).sum(-1)
         return p, p * (1.0 - p)
+
+
+class MultiClass(_NonGaussian):
+    """y in {0, ..., C - 1} with the robust-max likelihood (Hernandez-Lobato et al. 2011) over C = num_classes latent functions:
+    p(y | f) = 1 - epsilon if y = argmax_c f_c, else epsilon / (C - 1).  The likelihood COUPLES the latent columns of a row, so
+    a model asks for `num_latent` columns and calls variational_expectation / predict_mean_variance with all of them; the
+    per-column propagate_log does not apply.  Under q(f_c) = N(mu_c, v) with ONE variance per row (SVGP's marginals: S_L is
+    shared by the columns) and the rule's nodes x_h and weights w_h:
+
+        P = pi^-1/2 sum_h w_h prod_{c != y} Phi((mu_y - mu_c) / sqrt(v) + sqrt(2) x_h)      (the labelled latent is the largest)
+        <log p(y | f)> = P log(1 - epsilon) + (1 - P) log(epsilon / (C - 1))
+
+    -- linear in P, so nothing is ill-conditioned where P is tiny; far on the wrong side P and its gradients are exactly 0.  On
+    the GPU an instance of exactly this type evaluates both methods with one fused launch each (csrc/multiclass.hip)."""
+
+    def __init__(self, num_classes, epsilon=1e-3):
+        super().__init__()
+        if not (isinstance(num_classes, (int, np.integer)) and num_classes >= 2):
+            raise ValueError("num_classes must be an integer >= 2; got %r" % (num_classes,))
+        if not 0.0 < float(epsilon) < 1.0:
+            raise ValueError("epsilon must lie in (0, 1); got %r" % (epsilon,))
+        self.num_classes = int(num_classes)
+        self.epsilon = float(epsilon)
+
+    @property
+    def num_latent(self):
+        return self.num_classes
+
+    def _log_hit_miss(self):
+        return math.log1p(-self.epsilon), math.log(self.epsilon / (self.num_classes - 1))
+
+    def check_labels(self, Y):
+        """Y [n, 1] (or [n]) must hold integers in [0, num_classes): ValueError otherwise."""
+        Y = torch.as_tensor(Y)
+        if not (Y.dim() == 1 or (Y.dim() == 2 and Y.shape[1] == 1)):
+            raise ValueError("MultiClass expects one column of class labels; got shape %s" % (tuple(Y.shape),))
+        if Y.numel() and not bool(((Y >= 0) & (Y < self.num_classes) & (Y == torch.floor(Y))).all()):
+            raise ValueError("MultiClass labels must be integers in [0, %d)" % self.num_classes)
+
+    def _native(self, t):
+        from .models import sparse_gpr
+        return sparse_gpr.NATIVE_EXPECTATION and t.is_cuda and type(self) is MultiClass
+
+    def _check_marginals(self, f_mean, f_var):
+        if f_mean.dim() != 2 or f_mean.shape[1] != self.num_classes:
+            raise ValueError("expect means of shape [n, %d]; got %s" % (self.num_classes, tuple(f_mean.shape)))
+        if f_var.dim() == 2:                                  # [n, 1], or one shared variance expanded over the columns
+            f_var = f_var[:, 0]
+        if f_var.shape != (f_mean.shape[0],):
+            raise ValueError("expect one variance per row; got %s for %d rows" % (tuple(f_var.shape), f_mean.shape[0]))
+        return f_var
+
+    def _largest(self, f_mean, f_var, idx):
+        """-> P [n]: the rule's probability that column idx[i] is the largest of row i."""
+        x, w = gauss_hermite(self.num_gauss_hermite_points, f_mean.device)
+        gap = (f_mean.gather(1, idx[:, None]) - f_mean) / torch.sqrt(f_var)[:, None]                 # [n, C]
+        lp = _LogNdtr.apply(gap.unsqueeze(1) + (math.sqrt(2.0) * x)[None, :, None])                  # [n, H, C]
+        own = torch.nn.functional.one_hot(idx, self.num_classes).bool().unsqueeze(1)
+        return (torch.exp(lp.masked_fill(own, 0.0).sum(-1)) * w).sum(-1) * (1.0 / math.sqrt(math.pi))
+
+    def variational_expectation(self, f_mean, f_var, labels):
+        """<log p(y | f)> under N(f_mean [n, C], f_var [n]) summed over the rows (0-dim); labels [n] (or [n, 1])."""
+        f_var = self._check_marginals(f_mean, f_var)
+        labels = labels.reshape(-1)
+        if labels.shape[0] != f_mean.shape[0]:
+            raise ValueError("Targets (%i) and q(f) (%i rows) have mismatch in size" % (labels.shape[0], f_mean.shape[0]))
+        if self._native(f_mean):
+            from .models import sparse_gpr
+            return sparse_gpr._RobustMaxNode.apply(self.epsilon, self.num_gauss_hermite_points, f_mean, f_var, labels)
+        hit, miss = self._log_hit_miss()
+        P = self._largest(f_mean, f_var, labels.long())
+        return (P * hit + (1.0 - P) * miss).sum()
+
+    def predict_mean_variance(self, mean_f, var_f):
+        """-> (p [n, C], p (1 - p)) with p[:, c] = (1 - epsilon) P_c + epsilon / (C - 1) (1 - P_c), P_c the rule's probability
+        that column c is the largest.  The C probabilities of a row add to 1 only to the accuracy of the rule (exactly for
+        C = 2, where the rule is symmetric); they are returned as they are, not renormalised."""
+        var_f = self._check_marginals(mean_f, var_f)
+        if self._native(mean_f):
+            from . import _ops
+            x, w = gauss_hermite(self.num_gauss_hermite_points, mean_f.device)
+            p = _ops.lik_robustmax_probs(mean_f.detach(), var_f.detach(), self.epsilon, x, w)
+        else:
+            miss = self.epsilon / (self.num_classes - 1)
+            cols = []
+            for c in range(self.num_classes):
+                P = self._largest(mean_f, var_f, torch.full((mean_f.shape[0],), c, dtype=torch.long, device=mean_f.device))
+                cols.append((1.0 - self.epsilon) * P + miss * (1.0 - P))
+            p = torch.stack(cols, 1)
+        return p, p * (1.0 - p)
+
+    def logp(self, F, Y):
+        """the pointwise definition: F [..., C], Y [...] or [..., 1] -> log p(y | f) of Y's shape."""
+        hit, miss = self._log_hit_miss()
+        labels = Y.reshape(F.shape[:-1]).long()
+        lp = torch.where(torch.argmax(F, -1) == labels, torch.full_like(F[..., 0], hit), torch.full_like(F[..., 0], miss))
+        return lp.reshape(Y.shape)
+
+    def propagate_log(self, qf, targets):
+        raise NotImplementedError("MultiClass couples the latent columns of a row: propagate_log's contract is one column at a "
+                                  "time; use variational_expectation(f_mean [n, C], f_var [n], labels [n])")
 
 
 class Poisson(_NonGaussian):

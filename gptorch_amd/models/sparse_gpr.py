@@ -657,6 +657,24 @@ class _LikExpectNode(torch.autograd.Function):
         return (None, None, None, g * g_mean, g * g_var, None) + tuple((g * g_params[1]).reshape(s) for s in ctx.shapes)
 
 
+class _RobustMaxNode(torch.autograd.Function):
+    """likelihoods.MultiClass.variational_expectation as one autograd node over (f_mean [nb, C], f_var [nb]):
+    gpn_lik_expect_robustmax once in the forward (csrc/multiclass.hip), which also leaves the gradients."""
+
+    @staticmethod
+    def forward(ctx, eps, H, f_mean, f_var, labels):
+        nodes, weights = _likelihood_rule(H, f_mean.device)
+        value, g_mean, g_var = _ops.lik_expect_robustmax(f_mean.detach(), f_var.detach(), labels.detach(), eps, nodes, weights)
+        ctx.save_for_backward(g_mean, g_var)
+        return value
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        g_mean, g_var = ctx.saved_tensors
+        return None, None, g * g_mean, g * g_var, None
+
+
 def _likelihood_rule(H, device):
     from .. import likelihoods
     return likelihoods.gauss_hermite(H, device)
@@ -900,6 +918,11 @@ class SVGP(_InducingPointsGP):
                          mean_function=mean_function,
                          likelihood=likelihood if likelihood is not None else likelihoods.Gaussian())   # sparse_gpr.py:238
         self.batch_size = batch_size
+        # a likelihood that couples the latent columns of a row (likelihoods.MultiClass) says how many there are; Y is then ONE
+        # column of class labels, checked here once
+        self._coupled = getattr(self.likelihood, "num_latent", None) is not None
+        if self._coupled:
+            self.likelihood.check_labels(self.Y)
         # (induced_output_mean does NOT include the mean function's contribution, sparse_gpr.py:257-261)
         self.induced_output_mean, self.induced_output_chol_cov = self._init_posterior()
 
@@ -911,6 +934,8 @@ class SVGP(_InducingPointsGP):
         with torch.no_grad():
             x, y = self.X[i].detach().cpu(), self.Y[i].detach().cpu()
             Z = self.Z.detach().cpu()
+            if self._coupled:                                # regress on the one-hot targets: one latent column per class
+                y = torch.nn.functional.one_hot(y[:, 0].long(), self.likelihood.num_latent).to(torch.float64)
             if isinstance(self.likelihood, likelihoods.Gaussian):
                 s2 = self.likelihood.variance.transform().detach().cpu()
             else:
@@ -941,6 +966,8 @@ class SVGP(_InducingPointsGP):
             n = y.nelement()
             return (-0.5 * (n * (math.log(2.0 * math.pi) + torch.log(s2))
                             + (torch.sum((y - f_mean) ** 2) + y.shape[1] * f_var.sum()) / s2)).reshape(())
+        if self._coupled:                                    # (MultiClass on the GPU: gpn_lik_expect_robustmax, under the same switch)
+            return lik.variational_expectation(f_mean, f_var, y[:, 0]).reshape(())
         native = _native_likelihood(lik) if NATIVE_EXPECTATION and f_mean.is_cuda else None
         if native is not None:
             kind, df, tensors = native
