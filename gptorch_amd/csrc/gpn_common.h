@@ -101,11 +101,9 @@ int pack_rhs_full(hipStream_t s, const double* Y, const double* M, int64_t n, in
 // K(X) + noise I (lower tiles) into A and into Ksave (kmat.hip; gpn_lml_forward_saving)
 int assemble_lower_saving(hipStream_t s, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
                           int nls, const double* noise, double* A, double* Ksave, int64_t lda);
-// I + diag(sc) K(X) diag(sc), the entries on and below the diagonal only (kmat.hip; gpn_laplace_system)
-int assemble_laplace_system(hipStream_t s, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
-                            int nls, const double* sc, double* A, int64_t lda);
-// ... of `batch` models in one launch: points X + b sX (0: shared), variance[b], length_scales + b nls, sc + b sSc, slot A + b sA
-// (kmat.hip; gpn_laplace_system_batched)
+// I + diag(sc) K(X) diag(sc), the entries on and below the diagonal only, of `batch` models in one launch: points X + b sX (0:
+// shared), variance[b], length_scales + b nls, sc + b sSc, slot A + b sA (kmat.hip; gpn_laplace_system with batch = 1 and zero
+// strides, gpn_laplace_system_batched)
 int assemble_laplace_system_batched(hipStream_t s, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                                     const double* variance, const double* length_scales, int nls, const double* sc, int64_t sSc,
                                     double* A, int64_t lda, int64_t sA);

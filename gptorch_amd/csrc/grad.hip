@@ -427,7 +427,7 @@ __global__ __launch_bounds__(256) void grad_reduce_kernel(const double* partial,
 }
 
 template <int KIND, bool LML>
-static int launch_sweep(hipStream_t s, const GradArgs& a, int64_t nblocks, int batch = 1) {
+static int launch_sweep(hipStream_t s, const GradArgs& a, int64_t nblocks, int batch) {
   const int nch = (a.d + GDC - 1) / GDC;
   int rec = -1;
   if (profile_on())   // algorithmic bytes: the gradient matrix is read once (lower triangle for the LML sweep)
@@ -449,17 +449,42 @@ static int launch_sweep(hipStream_t s, const GradArgs& a, int64_t nblocks, int b
   return GPN_OK;
 }
 
+// workgroups (= partial-sum rows) per model: the tiles on and below the diagonal (LML mode) or all of them
+static int64_t grad_blocks(int64_t n, int64_t m, bool lml) {
+  const int64_t tm = (n + GT - 1) / GT, tn = (m + GT - 1) / GT;
+  return lml ? tm * (tm + 1) / 2 : tm * tn;
+}
+
+// the operands of a dense-mode sweep: model b of a lock-step launch reads X + b sX (0: shared points), X2 + b sX2 (X2 == nullptr:
+// the symmetric case, m = n), variance[b], ls + b nls, G + b sG; a single call passes zero strides.  (LML mode: G = Kinv; the
+// caller adds at, ldat, sAt, dy and n_of.)
+static GradArgs grad_args(const double* X, int64_t sX, int64_t n, const double* X2, int64_t sX2, int64_t m, int d, const double* variance,
+                          const double* length_scales, int nls, const double* G, int64_t ldg, int64_t sG, double* work) {
+  const bool symmetric = (X2 == nullptr);
+  GradArgs a;
+  a.X = X; a.X2 = symmetric ? X : X2; a.variance = variance; a.ls = length_scales;
+  a.G = G; a.ldg = ldg; a.at = nullptr; a.ldat = 0; a.partial = work;
+  a.n = (int)n; a.m = (int)(symmetric ? n : m); a.d = d; a.nls = nls; a.dy = 0; a.nout = 2 + nls;
+  a.tiles_m = (int)((a.n + GT - 1) / GT);
+  a.tiles_n = (int)((a.m + GT - 1) / GT);
+  a.sX = sX; a.sX2 = symmetric ? sX : sX2; a.sG = sG;
+  return a;
+}
+
+// the sweep of `batch` models in one launch (gridDim.y) and the reduce of their partial sums (sWork doubles apart; 0: back to
+// back) into out [batch, 2 + nls] (LML: with d/d(noise)) or [batch, 1 + nls].  Per model the same blocks, the same partial sums
+// in the same order, whatever the batch.
 template <bool LML>
-static int dispatch_kind(hipStream_t s, int kind, const GradArgs& a, int64_t nblocks, int batch = 1) {
-  switch (kind) {
-    case GPN_RBF: return launch_sweep<GPN_RBF, LML>(s, a, nblocks, batch);
-    case GPN_MATERN52: return launch_sweep<GPN_MATERN52, LML>(s, a, nblocks, batch);
-    case GPN_MATERN32: return launch_sweep<GPN_MATERN32, LML>(s, a, nblocks, batch);
-    case GPN_EXP: return launch_sweep<GPN_EXP, LML>(s, a, nblocks, batch);
-    case GPN_PERIODIC: return launch_sweep<GPN_PERIODIC, LML>(s, a, nblocks, batch);
-    case GPN_SQDIST: return launch_sweep<GPN_SQDIST, LML>(s, a, nblocks, batch);
-    default: return -2;
-  }
+static int grad_launch(hipStream_t s, int kind, int batch, GradArgs a, int64_t sWork, double* out) {
+  const int64_t nblocks = grad_blocks(a.n, a.m, LML);
+  const int nred = LML ? a.nout : 1 + a.nls;
+  a.sPartial = sWork > 0 ? sWork : nblocks * a.nout;
+  const int rc = with_kind<true>(kind, [&](auto k) -> int { return launch_sweep<decltype(k)::value, LML>(s, a, nblocks, batch); });
+  if (rc != GPN_OK) return rc;
+  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)nred, (unsigned)batch), dim3(256), 0, s, a.partial, nblocks, a.nout, out,
+                     a.sPartial, nred);
+  GPN_LAUNCH_CHECK();
+  return GPN_OK;
 }
 
 // ---- gradient w.r.t. the points of the second argument --------------------------------
@@ -668,6 +693,29 @@ static int launch_x2(hipStream_t s, const GradX2Args& a, dim3 grid) {
   return GPN_OK;
 }
 
+// the slab sweep of `batch` models in one launch (gridDim.z; batch > 1: d <= GMAXD) and the reduce of their slabs into
+// out [batch, m, d]: model b reads X + b sX, X2 + b sX2, variance[b], ls + b nls, G + b sG; a single call passes zero strides
+static int grad_x2_launch(hipStream_t s, int kind, int batch, const double* X, int64_t sX, int64_t n, const double* X2, int64_t sX2,
+                          int64_t m, int d, const double* variance, const double* length_scales, int nls, const double* G, int64_t ldg,
+                          int64_t sG, double scale, int accumulate, double* work, double* out) {
+  GradX2Args a;
+  a.X = X; a.X2 = X2; a.variance = variance; a.ls = length_scales; a.G = G; a.ldg = ldg; a.partial = work;
+  a.n = (int)n; a.m = (int)m; a.d = d; a.nls = nls;
+  const int slabs = x2_slabs(n, m);
+  const int64_t row_tiles = (n + GT - 1) / GT;
+  a.slab_rows = (int)((row_tiles + slabs - 1) / slabs) * GT;
+  const int used = (int)((n + a.slab_rows - 1) / a.slab_rows);   // <= slabs
+  const int64_t md = m * (int64_t)d;
+  a.batch = batch; a.sX = sX; a.sX2 = sX2; a.sG = sG; a.sPartial = slabs * md;
+  const dim3 grid((unsigned)((m + GT - 1) / GT), (unsigned)used, (unsigned)batch);
+  const int rc = with_kind<true>(kind, [&](auto k) -> int { return launch_x2<decltype(k)::value>(s, a, grid); });
+  if (rc != GPN_OK) return rc;
+  hipLaunchKernelGGL(grad_x2_reduce_kernel, dim3((unsigned)((md + 255) / 256), (unsigned)batch), dim3(256), 0, s, work, used, md, scale,
+                     accumulate, out, a.sPartial);
+  GPN_LAUNCH_CHECK();
+  return GPN_OK;
+}
+
 }  // namespace gpn
 
 using namespace gpn;
@@ -693,38 +741,13 @@ extern "C" int gpn_kernel_grad_x2(void* stream, int kind, const double* X, int64
   if (ldg < m) return -12;
   if (!work) return -15;
   if (!out) return -16;
-  GradX2Args a;
-  a.X = X; a.X2 = X2; a.variance = variance; a.ls = length_scales; a.G = G; a.ldg = ldg; a.partial = work;
-  a.n = (int)n; a.m = (int)m; a.d = d; a.nls = nls;
-  const int slabs = x2_slabs(n, m);
-  const int64_t row_tiles = (n + GT - 1) / GT;
-  a.slab_rows = (int)((row_tiles + slabs - 1) / slabs) * GT;
-  const int used = (int)((n + a.slab_rows - 1) / a.slab_rows);   // <= slabs
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  dim3 grid((unsigned)((m + GT - 1) / GT), (unsigned)used);
-  int rc;
-  switch (kind) {
-    case GPN_RBF: rc = launch_x2<GPN_RBF>(s, a, grid); break;
-    case GPN_MATERN52: rc = launch_x2<GPN_MATERN52>(s, a, grid); break;
-    case GPN_MATERN32: rc = launch_x2<GPN_MATERN32>(s, a, grid); break;
-    case GPN_EXP: rc = launch_x2<GPN_EXP>(s, a, grid); break;
-    case GPN_PERIODIC: rc = launch_x2<GPN_PERIODIC>(s, a, grid); break;
-    case GPN_SQDIST: rc = launch_x2<GPN_SQDIST>(s, a, grid); break;
-    default: return -2;
-  }
-  if (rc != GPN_OK) return rc;
-  const int64_t md = m * (int64_t)d;
-  hipLaunchKernelGGL(grad_x2_reduce_kernel, dim3((unsigned)((md + 255) / 256)), dim3(256), 0, s, work, used, md, scale,
-                     accumulate, out);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  return grad_x2_launch(static_cast<hipStream_t>(stream), kind, 1, X, 0, n, X2, 0, m, d, variance, length_scales, nls, G, ldg, 0, scale,
+                        accumulate, work, out);
 }
 
 
 extern "C" int64_t gpn_grad_work_bytes(int64_t n, int64_t m, int nls, int lml) {
-  const int64_t tm = (n + GT - 1) / GT, tn = (m + GT - 1) / GT;
-  const int64_t blocks = lml ? tm * (tm + 1) / 2 : tm * tn;
-  return blocks * (int64_t)(2 + nls) * (int64_t)sizeof(double);
+  return grad_blocks(n, m, lml != 0) * (int64_t)(2 + nls) * (int64_t)sizeof(double);
 }
 
 extern "C" int gpn_lml_grad(void* stream, int kind, const double* X, int64_t n, int d,
@@ -744,18 +767,9 @@ extern "C" int gpn_lml_grad(void* stream, int kind, const double* X, int64_t n, 
   if (dy <= 0) return -13;
   if (!work) return -14;
   if (!out) return -15;
-  GradArgs a;
-  a.X = X; a.X2 = X; a.variance = variance; a.ls = length_scales;
-  a.G = Kinv; a.ldg = ldk; a.at = at; a.ldat = ldat; a.partial = work;
-  a.n = (int)n; a.m = (int)n; a.d = d; a.nls = nls; a.dy = dy; a.nout = 2 + nls;
-  a.tiles_m = a.tiles_n = (int)((n + GT - 1) / GT);
-  const int64_t nblocks = (int64_t)a.tiles_m * (a.tiles_m + 1) / 2;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int rc = dispatch_kind<true>(s, kind, a, nblocks);
-  if (rc != GPN_OK) return rc;
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)a.nout), dim3(256), 0, s, work, nblocks, a.nout, out, (int64_t)0, 0);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  GradArgs a = grad_args(X, 0, n, nullptr, 0, n, d, variance, length_scales, nls, Kinv, ldk, 0, work);
+  a.at = at; a.ldat = ldat; a.dy = dy;
+  return grad_launch<true>(static_cast<hipStream_t>(stream), kind, 1, a, 0, out);
 }
 
 // gpn_lml_grad for `batch` lock-step models in ONE sweep launch (gridDim.y = batch) + one reduction launch: model b reads
@@ -790,21 +804,10 @@ int gpn::lml_grad_batched(hipStream_t s, int kind, int batch, const double* X, i
   if (!work) return -18;
   if (!out) return -19;
   if (batch > 65535) return GPN_E_UNSUPPORTED;
-  GradArgs a;
-  a.X = X; a.X2 = X; a.variance = variance; a.ls = length_scales;
-  a.G = Kinv; a.ldg = ldk; a.at = at; a.ldat = ldat; a.partial = work;
-  a.n = (int)n; a.m = (int)n; a.d = d; a.nls = nls; a.dy = dy; a.nout = 2 + nls;
-  a.tiles_m = a.tiles_n = (int)((n + GT - 1) / GT);
-  const int64_t nblocks = (int64_t)a.tiles_m * (a.tiles_m + 1) / 2;
-  a.sX = sX; a.sG = sK; a.sAt = sAt; a.sPartial = sWork > 0 ? sWork : nblocks * a.nout;
-  a.n_of = n_of;
-  if (sWork > 0 && sWork < nblocks * a.nout) return -18;
-  const int rc = dispatch_kind<true>(s, kind, a, nblocks, batch);
-  if (rc != GPN_OK) return rc;
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)a.nout, (unsigned)batch), dim3(256), 0, s, work, nblocks, a.nout, out,
-                     a.sPartial, a.nout);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  if (sWork > 0 && sWork < grad_blocks(n, n, true) * (2 + nls)) return -18;
+  GradArgs a = grad_args(X, sX, n, nullptr, 0, n, d, variance, length_scales, nls, Kinv, ldk, sK, work);
+  a.at = at; a.ldat = ldat; a.sAt = sAt; a.dy = dy; a.n_of = n_of;
+  return grad_launch<true>(s, kind, batch, a, sWork, out);
 }
 
 extern "C" int gpn_kernel_grad(void* stream, int kind, const double* X, int64_t n, const double* X2, int64_t m, int d,
@@ -812,8 +815,7 @@ extern "C" int gpn_kernel_grad(void* stream, int kind, const double* X, int64_t 
                                const double* G, int64_t ldg, double* work, double* out) {
   if (!X) return -3;
   if (n <= 0) return -4;
-  const bool symmetric = (X2 == nullptr);
-  if (symmetric) m = n;
+  if (!X2) m = n;
   if (m <= 0) return -6;
   if (d <= 0) return -7;
   if (!variance) return -8;
@@ -823,19 +825,8 @@ extern "C" int gpn_kernel_grad(void* stream, int kind, const double* X, int64_t 
   if (ldg < m) return -12;
   if (!work) return -13;
   if (!out) return -14;
-  GradArgs a;
-  a.X = X; a.X2 = symmetric ? X : X2; a.variance = variance; a.ls = length_scales;
-  a.G = G; a.ldg = ldg; a.at = nullptr; a.ldat = 0; a.partial = work;
-  a.n = (int)n; a.m = (int)m; a.d = d; a.nls = nls; a.dy = 0; a.nout = 2 + nls;
-  a.tiles_m = (int)((n + GT - 1) / GT);
-  a.tiles_n = (int)((m + GT - 1) / GT);
-  const int64_t nblocks = (int64_t)a.tiles_m * a.tiles_n;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int rc = dispatch_kind<false>(s, kind, a, nblocks);
-  if (rc != GPN_OK) return rc;
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(1 + nls)), dim3(256), 0, s, work, nblocks, a.nout, out, (int64_t)0, 0);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  const GradArgs a = grad_args(X, 0, n, X2, 0, m, d, variance, length_scales, nls, G, ldg, 0, work);
+  return grad_launch<false>(static_cast<hipStream_t>(stream), kind, 1, a, 0, out);
 }
 
 // gpn_kernel_grad for `batch` models in ONE sweep launch (gridDim.y) + one reduction launch: model b reads X + b sX (0: shared
@@ -849,8 +840,7 @@ extern "C" int gpn_kernel_grad_batched(void* stream, int kind, int batch, const 
   if (batch < 1 || batch > 65535) return -3;
   if (!X) return -4;
   if (n <= 0) return -6;
-  const bool symmetric = (X2 == nullptr);
-  if (symmetric) m = n;
+  if (!X2) m = n;
   if (m <= 0) return -9;
   if (d <= 0) return -10;
   if (!variance) return -11;
@@ -860,21 +850,8 @@ extern "C" int gpn_kernel_grad_batched(void* stream, int kind, int batch, const 
   if (ldg < m) return -15;
   if (!work) return -17;
   if (!out) return -18;
-  GradArgs a;
-  a.X = X; a.X2 = symmetric ? X : X2; a.variance = variance; a.ls = length_scales;
-  a.G = G; a.ldg = ldg; a.at = nullptr; a.ldat = 0; a.partial = work;
-  a.n = (int)n; a.m = (int)m; a.d = d; a.nls = nls; a.dy = 0; a.nout = 2 + nls;
-  a.tiles_m = (int)((n + GT - 1) / GT);
-  a.tiles_n = (int)((m + GT - 1) / GT);
-  const int64_t nblocks = (int64_t)a.tiles_m * a.tiles_n;
-  a.sX = sX; a.sX2 = symmetric ? sX : sX2; a.sG = sG; a.sAt = 0; a.sPartial = nblocks * a.nout;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int rc = dispatch_kind<false>(s, kind, a, nblocks, batch);
-  if (rc != GPN_OK) return rc;
-  hipLaunchKernelGGL(grad_reduce_kernel, dim3((unsigned)(1 + nls), (unsigned)batch), dim3(256), 0, s, work, nblocks, a.nout, out,
-                     a.sPartial, 1 + nls);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  const GradArgs a = grad_args(X, sX, n, X2, sX2, m, d, variance, length_scales, nls, G, ldg, sG, work);
+  return grad_launch<false>(static_cast<hipStream_t>(stream), kind, batch, a, 0, out);
 }
 
 // gpn_kernel_grad_x2 for `batch` models: out + b m d (+)= scale * ...; work: batch * gpn_grad_x2_work_bytes(n, m, d).  Up to 64
@@ -898,39 +875,14 @@ extern "C" int gpn_kernel_grad_x2_batched(void* stream, int kind, int batch, con
   if (ldg < m) return -15;
   if (!work) return -19;
   if (!out) return -20;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (d <= GMAXD) return grad_x2_launch(s, kind, batch, X, sX, n, X2, sX2, m, d, variance, length_scales, nls, G, ldg, sG, scale, accumulate, work, out);
   const int64_t md = m * (int64_t)d;
   const int64_t one = gpn_grad_x2_work_bytes(n, m, d) / (int64_t)sizeof(double);
-  if (batch == 1 || d > GMAXD) {
-    for (int z = 0; z < batch; ++z) {
-      const int rc = gpn_kernel_grad_x2(stream, kind, X + z * sX, n, X2 + z * sX2, m, d, variance + z, length_scales + (int64_t)z * nls, nls,
-                                        G + z * sG, ldg, scale, accumulate, work + z * one, out + z * md);
-      if (rc != GPN_OK) return rc;
-    }
-    return GPN_OK;
+  for (int z = 0; z < batch; ++z) {              // (the chunked kernel's gridDim.z = coordinate blocks)
+    const int rc = grad_x2_launch(s, kind, 1, X + z * sX, 0, n, X2 + z * sX2, 0, m, d, variance + z, length_scales + (int64_t)z * nls, nls,
+                                  G + z * sG, ldg, 0, scale, accumulate, work + z * one, out + z * md);
+    if (rc != GPN_OK) return rc;
   }
-  GradX2Args a;
-  a.X = X; a.X2 = X2; a.variance = variance; a.ls = length_scales; a.G = G; a.ldg = ldg; a.partial = work;
-  a.n = (int)n; a.m = (int)m; a.d = d; a.nls = nls;
-  const int slabs = x2_slabs(n, m);
-  const int64_t row_tiles = (n + GT - 1) / GT;
-  a.slab_rows = (int)((row_tiles + slabs - 1) / slabs) * GT;
-  const int used = (int)((n + a.slab_rows - 1) / a.slab_rows);
-  a.batch = batch; a.sX = sX; a.sX2 = sX2; a.sG = sG; a.sPartial = one;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  dim3 grid((unsigned)((m + GT - 1) / GT), (unsigned)used, (unsigned)batch);
-  int rc;
-  switch (kind) {
-    case GPN_RBF: rc = launch_x2<GPN_RBF>(s, a, grid); break;
-    case GPN_MATERN52: rc = launch_x2<GPN_MATERN52>(s, a, grid); break;
-    case GPN_MATERN32: rc = launch_x2<GPN_MATERN32>(s, a, grid); break;
-    case GPN_EXP: rc = launch_x2<GPN_EXP>(s, a, grid); break;
-    case GPN_PERIODIC: rc = launch_x2<GPN_PERIODIC>(s, a, grid); break;
-    case GPN_SQDIST: rc = launch_x2<GPN_SQDIST>(s, a, grid); break;
-    default: return -2;
-  }
-  if (rc != GPN_OK) return rc;
-  hipLaunchKernelGGL(grad_x2_reduce_kernel, dim3((unsigned)((md + 255) / 256), (unsigned)batch), dim3(256), 0, s, work, used, md, scale,
-                     accumulate, out, one);
-  GPN_LAUNCH_CHECK();
   return GPN_OK;
 }

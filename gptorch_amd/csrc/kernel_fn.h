@@ -1,9 +1,33 @@
-// The stationary kernels as functions of the scaled squared distance -- ONE definition shared by the assembly
-// (kmat.hip) and the refinement's residual pass (refine.hip), which must reproduce the assembled entries bit for bit.
+// The stationary kernels as functions of the scaled squared distance -- ONE definition of the formulas and ONE place where a
+// run-time kind becomes a template argument:
+//   kernel_of_r2  the assembly (kmat.hip), the refinement's residual pass (refine.hip), which must reproduce the assembled
+//                 entries bit for bit, LaplaceGP's row sweeps (laplace.hip) and the expression leaves (kexpr.hip)
+//   k_and_base    the gradient sweeps (grad.hip, laplace.hip, loo.hip, kexpr.hip)
+//   with_kind     every host function of those files that launches a kernel instantiated per kind
 #pragma once
+#include <type_traits>
 #include "gpn_common.h"
 
 namespace gpn {
+
+// f(std::integral_constant<int, KIND>{}) for the run-time kind; -2 (the kind's argument position in every entry point) for a
+// kind that is not served: anything out of range, and GPN_SQDIST unless SQDIST_TOO (the assembly and the gradient sweeps have
+// a SqDist instantiation, nothing that factors or solves against K does: kind_is_covariance, gpn_common.h).  f runs only for
+// a served kind, so whatever it opens (a profile record) it also closes.
+template <bool SQDIST_TOO = false, class F>
+inline int with_kind(int kind, F&& f) {
+  switch (kind) {
+    case GPN_RBF: return f(std::integral_constant<int, GPN_RBF>{});
+    case GPN_MATERN52: return f(std::integral_constant<int, GPN_MATERN52>{});
+    case GPN_MATERN32: return f(std::integral_constant<int, GPN_MATERN32>{});
+    case GPN_EXP: return f(std::integral_constant<int, GPN_EXP>{});
+    case GPN_PERIODIC: return f(std::integral_constant<int, GPN_PERIODIC>{});
+    case GPN_SQDIST:
+      if constexpr (SQDIST_TOO) return f(std::integral_constant<int, GPN_SQDIST>{});
+      else return -2;
+    default: return -2;
+  }
+}
 
 template <int KIND>
 __device__ __forceinline__ double kernel_of_r2(double r2, double var) {

@@ -40,26 +40,14 @@ __device__ __forceinline__ double stationary_value(int kind, double r2, double v
   }
 }
 
-// K and B = the factor of dK/d ell_d = B s_d / ell_d (grad.hip k_and_base), kind at run time
+// K and B = the factor of dK/d ell_d = B s_d / ell_d (kernel_fn.h k_and_base), kind at run time
 __device__ __forceinline__ void stationary_k_b(int kind, double r2, double var, double& K, double& B) {
-  if (kind == GPN_RBF) { K = var * exp(-0.5 * r2); B = K; return; }
-  const bool dead = r2 < 1e-40;                  // kernels.py:172 clamp: no gradient below it
-  const double r = sqrt(fmax(r2, 1e-40));
-  if (kind == GPN_MATERN52) {
-    const double s5 = 2.23606797749978969641, e = exp(-s5 * r);
-    K = var * (1.0 + s5 * r + 5.0 / 3.0 * r * r) * e;
-    B = dead ? 0.0 : var * (5.0 / 3.0) * (1.0 + s5 * r) * e;
-  } else if (kind == GPN_MATERN32) {
-    const double s3 = 1.73205080756887729353, e = exp(-s3 * r);
-    K = var * (1.0 + s3 * r) * e;
-    B = dead ? 0.0 : 3.0 * var * e;
-  } else if (kind == GPN_PERIODIC) {
-    K = var * cos(r);
-    B = dead ? 0.0 : var * sin(r) / r;
-  } else {
-    const double e = exp(-r);
-    K = var * e;
-    B = dead ? 0.0 : var * e / r;
+  switch (kind) {
+    case GPN_RBF: return k_and_base<GPN_RBF>(r2, var, K, B);
+    case GPN_MATERN52: return k_and_base<GPN_MATERN52>(r2, var, K, B);
+    case GPN_MATERN32: return k_and_base<GPN_MATERN32>(r2, var, K, B);
+    case GPN_PERIODIC: return k_and_base<GPN_PERIODIC>(r2, var, K, B);
+    default: return k_and_base<GPN_EXP>(r2, var, K, B);
   }
 }
 

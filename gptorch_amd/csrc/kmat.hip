@@ -218,122 +218,69 @@ int pack_rhs_full(hipStream_t s, const double* Y, const double* M, int64_t n, in
   return GPN_OK;
 }
 
+// the operands of every assembly: model b of a lock-step launch reads X + b sX (0: shared points), X2 + b sX2 (X2 == nullptr: the
+// symmetric case, m = n), variance[b], ls + b nls, noise[b] and writes K + b sK; a single call passes zero strides
+static KmatArgs kmat_args(const double* X, int64_t sX, int64_t n, const double* X2, int64_t sX2, int64_t m, int d, const double* variance,
+                          const double* length_scales, int nls, const double* noise, int lower, double* K, int64_t ldk, int64_t sK) {
+  const bool symmetric = (X2 == nullptr);
+  KmatArgs a;
+  a.X = X; a.X2 = symmetric ? X : X2;
+  a.variance = variance; a.ls = length_scales; a.noise = noise;
+  a.K = K; a.ldk = ldk;
+  a.n = (int)n; a.m = (int)(symmetric ? n : m); a.d = d; a.nls = nls;
+  a.symmetric = symmetric; a.lower = lower;
+  a.vec_ok = ((ldk & 1) == 0) && ((reinterpret_cast<uintptr_t>(K) & 15) == 0) && ((sK & 1) == 0);
+  a.sX = sX; a.sK = sK; a.sX2 = symmetric ? sX : sX2;
+  return a;
+}
+
+// one launch for `batch` models (gridDim.z): the tiles on and below the diagonal (a.lower) or all of them; per model the same
+// kernel, entry by entry, whatever the batch.  SQDIST_TOO: gpn_kernel_matrix{,_batched} only.
+template <bool LAPLACE = false, bool SQDIST_TOO = false>
+static int kmat_launch(hipStream_t s, int kind, const KmatArgs& a, int batch) {
+  const unsigned tn = (unsigned)((a.m + KT - 1) / KT), tm = (unsigned)((a.n + KT - 1) / KT);
+  if (!a.lower && tm > 65535) return GPN_E_UNSUPPORTED;        // (the row tiles are the grid's y dimension)
+  const dim3 grid = a.lower ? dim3(tm * (tm + 1) / 2, 1, (unsigned)batch) : dim3(tn, tm, (unsigned)batch);
+  return with_kind<SQDIST_TOO>(kind, [&](auto k) -> int {
+    const double n = a.n, m = a.m;
+    int rec = -1;
+    if (profile_on())   // algorithmic bytes: the entries written once + the points read once (a saved copy earns nothing)
+      rec = profile_begin(s, batch * (a.lower ? 8.0 * (0.5 * n * (n + 1.0) + n * a.d) : 8.0 * (n * m + (n + (a.symmetric ? 0.0 : m)) * a.d)),
+                          PROF_KMAT);
+    hipLaunchKernelGGL((kmat_kernel<decltype(k)::value, LAPLACE>), grid, dim3(256), 0, s, a);
+    if (rec >= 0) profile_end(s, rec);
+    GPN_LAUNCH_CHECK();
+    return GPN_OK;
+  });
+}
+
 // K(X) + noise I, lower tiles, into A AND into Ksave (same leading dimension): gpn_lml_forward_saving
 int assemble_lower_saving(hipStream_t s, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
                           int nls, const double* noise, double* A, double* Ksave, int64_t lda) {
-  if (!kind_is_covariance(kind)) return -2;
-  KmatArgs a;
-  a.X = X; a.X2 = X;
-  a.variance = variance; a.ls = length_scales; a.noise = noise;
-  a.K = A; a.K2 = Ksave; a.ldk = lda;
-  a.n = (int)n; a.m = (int)n; a.d = d; a.nls = nls;
-  a.symmetric = 1; a.lower = 1;
-  a.vec_ok = ((lda & 1) == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0) && ((reinterpret_cast<uintptr_t>(Ksave) & 15) == 0);
-  a.sX = 0; a.sK = 0;
-  const unsigned tm = (unsigned)((n + KT - 1) / KT);
-  const dim3 grid(tm * (tm + 1) / 2);
-  int rec = -1;
-  if (profile_on()) rec = profile_begin(s, 8.0 * (0.5 * n * (n + 1.0) + (double)n * d), PROF_KMAT);     // (algorithmic bytes: the copy earns nothing)
-  switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL(kmat_kernel<GPN_RBF>, grid, dim3(256), 0, s, a); break;
-    case GPN_MATERN52: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, a); break;
-    case GPN_MATERN32: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, a); break;
-    case GPN_EXP: hipLaunchKernelGGL(kmat_kernel<GPN_EXP>, grid, dim3(256), 0, s, a); break;
-    case GPN_PERIODIC: hipLaunchKernelGGL(kmat_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, a); break;
-    default: return -2;
-  }
-  if (rec >= 0) profile_end(s, rec);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  KmatArgs a = kmat_args(X, 0, n, nullptr, 0, n, d, variance, length_scales, nls, noise, 1, A, lda, 0);
+  a.K2 = Ksave;
+  a.vec_ok = a.vec_ok && ((reinterpret_cast<uintptr_t>(Ksave) & 15) == 0);
+  return kmat_launch(s, kind, a, 1);
 }
 
-// B = I + diag(sc) K(X) diag(sc), entries on and below the diagonal, into A (laplace.hip; gpn_laplace_system)
-int assemble_laplace_system(hipStream_t s, int kind, const double* X, int64_t n, int d, const double* variance, const double* length_scales,
-                            int nls, const double* sc, double* A, int64_t lda) {
-  if (!kind_is_covariance(kind)) return -2;       // (before the profile record opens: the switch below cannot leave it open)
-  KmatArgs a;
-  a.X = X; a.X2 = X;
-  a.variance = variance; a.ls = length_scales; a.noise = nullptr; a.sc = sc;
-  a.K = A; a.ldk = lda;
-  a.n = (int)n; a.m = (int)n; a.d = d; a.nls = nls;
-  a.symmetric = 1; a.lower = 1;
-  a.vec_ok = ((lda & 1) == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0);
-  a.sX = 0; a.sK = 0;
-  const unsigned tm = (unsigned)((n + KT - 1) / KT);
-  const dim3 grid(tm * (tm + 1) / 2);
-  int rec = -1;
-  if (profile_on()) rec = profile_begin(s, 8.0 * (0.5 * n * (n + 1.0) + (double)n * d), PROF_KMAT);
-  switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL((kmat_kernel<GPN_RBF, true>), grid, dim3(256), 0, s, a); break;
-    case GPN_MATERN52: hipLaunchKernelGGL((kmat_kernel<GPN_MATERN52, true>), grid, dim3(256), 0, s, a); break;
-    case GPN_MATERN32: hipLaunchKernelGGL((kmat_kernel<GPN_MATERN32, true>), grid, dim3(256), 0, s, a); break;
-    case GPN_EXP: hipLaunchKernelGGL((kmat_kernel<GPN_EXP, true>), grid, dim3(256), 0, s, a); break;
-    case GPN_PERIODIC: hipLaunchKernelGGL((kmat_kernel<GPN_PERIODIC, true>), grid, dim3(256), 0, s, a); break;
-    default: return -2;
-  }
-  if (rec >= 0) profile_end(s, rec);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
-}
-
-// assemble_laplace_system for `batch` models in one launch (gridDim.z): per model the same kernel, entry by entry
+// B_b = I + diag(sc_b) K(X_b) diag(sc_b), entries on and below the diagonal, into A + b sA (laplace.hip: gpn_laplace_system passes
+// batch = 1 and zero strides, gpn_laplace_system_batched its own)
 int assemble_laplace_system_batched(hipStream_t s, int kind, int batch, const double* X, int64_t sX, int64_t n, int d,
                                     const double* variance, const double* length_scales, int nls, const double* sc, int64_t sSc,
                                     double* A, int64_t lda, int64_t sA) {
-  if (!kind_is_covariance(kind)) return -2;       // (before the profile record opens: the switch below cannot leave it open)
-  KmatArgs a;
-  a.X = X; a.X2 = X;
-  a.variance = variance; a.ls = length_scales; a.noise = nullptr; a.sc = sc; a.sSc = sSc;
-  a.K = A; a.ldk = lda;
-  a.n = (int)n; a.m = (int)n; a.d = d; a.nls = nls;
-  a.symmetric = 1; a.lower = 1;
-  a.vec_ok = ((lda & 1) == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0) && ((sA & 1) == 0);
-  a.sX = sX; a.sK = sA;
-  const unsigned tm = (unsigned)((n + KT - 1) / KT);
-  const dim3 grid(tm * (tm + 1) / 2, 1, (unsigned)batch);
-  int rec = -1;
-  if (profile_on()) rec = profile_begin(s, batch * 8.0 * (0.5 * n * (n + 1.0) + (double)n * d), PROF_KMAT);
-  switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL((kmat_kernel<GPN_RBF, true>), grid, dim3(256), 0, s, a); break;
-    case GPN_MATERN52: hipLaunchKernelGGL((kmat_kernel<GPN_MATERN52, true>), grid, dim3(256), 0, s, a); break;
-    case GPN_MATERN32: hipLaunchKernelGGL((kmat_kernel<GPN_MATERN32, true>), grid, dim3(256), 0, s, a); break;
-    case GPN_EXP: hipLaunchKernelGGL((kmat_kernel<GPN_EXP, true>), grid, dim3(256), 0, s, a); break;
-    case GPN_PERIODIC: hipLaunchKernelGGL((kmat_kernel<GPN_PERIODIC, true>), grid, dim3(256), 0, s, a); break;
-    default: return -2;
-  }
-  if (rec >= 0) profile_end(s, rec);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  KmatArgs a = kmat_args(X, sX, n, nullptr, 0, n, d, variance, length_scales, nls, nullptr, 1, A, lda, sA);
+  a.sc = sc; a.sSc = sSc;
+  return kmat_launch<true>(s, kind, a, batch);
 }
 
 // symmetric K(X_b) + noise_b I, lower tiles, for `batch` models in one launch (+ their right-hand sides and info words)
 int assemble_batched(hipStream_t s, int kind, int batch, const double* X, int64_t sX, int64_t n, int d, const double* Y, int64_t sY,
                      const double* M, int64_t sM, int dy, const double* variance, const double* length_scales, int nls,
                      const double* noise, double* A, int64_t lda, int64_t sA, int32_t* info, const int32_t* n_of) {
-  if (!kind_is_covariance(kind)) return -2;       // (before the profile record opens: the switch below cannot leave it open)
-  KmatArgs a;
+  KmatArgs a = kmat_args(X, sX, n, nullptr, 0, n, d, variance, length_scales, nls, noise, 1, A, lda, sA);
   a.n_of = n_of;
-  a.X = X; a.X2 = X;
-  a.variance = variance; a.ls = length_scales; a.noise = noise;
-  a.K = A; a.ldk = lda;
-  a.n = (int)n; a.m = (int)n; a.d = d; a.nls = nls;
-  a.symmetric = 1; a.lower = 1;
-  a.vec_ok = ((lda & 1) == 0) && ((reinterpret_cast<uintptr_t>(A) & 15) == 0) && ((sA & 1) == 0);
-  a.sX = sX; a.sK = sA;
-  const unsigned tm = (unsigned)((n + KT - 1) / KT);
-  const dim3 grid(tm * (tm + 1) / 2, 1, (unsigned)batch);
-  int rec = -1;
-  if (profile_on()) rec = profile_begin(s, batch * 8.0 * (0.5 * n * (n + 1.0) + (double)n * d), PROF_KMAT);
-  switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL(kmat_kernel<GPN_RBF>, grid, dim3(256), 0, s, a); break;
-    case GPN_MATERN52: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, a); break;
-    case GPN_MATERN32: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, a); break;
-    case GPN_EXP: hipLaunchKernelGGL(kmat_kernel<GPN_EXP>, grid, dim3(256), 0, s, a); break;
-    case GPN_PERIODIC: hipLaunchKernelGGL(kmat_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, a); break;
-    default: return -2;
-  }
-  if (rec >= 0) profile_end(s, rec);
-  GPN_LAUNCH_CHECK();
+  const int rc = kmat_launch(s, kind, a, batch);
+  if (rc != GPN_OK) return rc;
   hipLaunchKernelGGL(pack_rhs_kernel, dim3((unsigned)((lda + 255) / 256), (unsigned)batch), dim3(256), 0, s, Y, M, n, dy,
                      A + n * lda, lda, 1, info, sY, sM, sA, n_of);
   GPN_LAUNCH_CHECK();
@@ -361,33 +308,8 @@ extern "C" int gpn_kernel_matrix(void* stream, int kind, const double* X, int64_
   if (!K) return -13;
   if (ldk < m) return -14;
   if (n == 0 || m == 0) return GPN_OK;
-  KmatArgs a;
-  a.X = X; a.X2 = symmetric ? X : X2;
-  a.variance = variance; a.ls = length_scales; a.noise = noise;
-  a.K = K; a.ldk = ldk;
-  a.n = (int)n; a.m = (int)m; a.d = d; a.nls = nls;
-  a.symmetric = symmetric; a.lower = (uplo == GPN_LOWER);
-  a.vec_ok = ((ldk & 1) == 0) && ((reinterpret_cast<uintptr_t>(K) & 15) == 0);
-  a.sX = 0; a.sK = 0;
-  const unsigned tn = (unsigned)((m + KT - 1) / KT), tm = (unsigned)((n + KT - 1) / KT);
-  dim3 grid = a.lower ? dim3(tm * (tm + 1) / 2) : dim3(tn, tm);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int rec = -1;
-  if (profile_on())   // algorithmic bytes: the entries written once + the points read once
-    rec = profile_begin(s, a.lower ? 8.0 * (0.5 * n * (n + 1.0) + (double)n * d) : 8.0 * ((double)n * m + (double)(n + (symmetric ? 0 : m)) * d),
-                        PROF_KMAT);
-  switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL(kmat_kernel<GPN_RBF>, grid, dim3(256), 0, s, a); break;
-    case GPN_MATERN52: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, a); break;
-    case GPN_MATERN32: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, a); break;
-    case GPN_EXP: hipLaunchKernelGGL(kmat_kernel<GPN_EXP>, grid, dim3(256), 0, s, a); break;
-    case GPN_PERIODIC: hipLaunchKernelGGL(kmat_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, a); break;
-    case GPN_SQDIST: hipLaunchKernelGGL(kmat_kernel<GPN_SQDIST>, grid, dim3(256), 0, s, a); break;
-    default: return -2;
-  }
-  if (rec >= 0) profile_end(s, rec);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  const KmatArgs a = kmat_args(X, 0, n, X2, 0, m, d, variance, length_scales, nls, noise, uplo == GPN_LOWER, K, ldk, 0);
+  return kmat_launch<false, true>(static_cast<hipStream_t>(stream), kind, a, 1);
 }
 
 // gpn_kernel_matrix for `batch` models in ONE launch (gridDim.z): model b reads X + b sX (sX = 0: shared points), X2 + b sX2,
@@ -415,34 +337,8 @@ extern "C" int gpn_kernel_matrix_batched(void* stream, int kind, int batch, cons
   if (ldk < m) return -17;
   if (batch > 1 && sK < (n - 1) * ldk + m) return -18;
   if (n == 0 || m == 0) return GPN_OK;
-  KmatArgs a;
-  a.X = X; a.X2 = symmetric ? X : X2;
-  a.variance = variance; a.ls = length_scales; a.noise = noise;
-  a.K = K; a.ldk = ldk;
-  a.n = (int)n; a.m = (int)m; a.d = d; a.nls = nls;
-  a.symmetric = symmetric; a.lower = (uplo == GPN_LOWER);
-  a.vec_ok = ((ldk & 1) == 0) && ((reinterpret_cast<uintptr_t>(K) & 15) == 0) && ((sK & 1) == 0);
-  a.sX = sX; a.sK = sK; a.sX2 = symmetric ? sX : sX2;
-  const unsigned tn = (unsigned)((m + KT - 1) / KT), tm = (unsigned)((n + KT - 1) / KT);
-  if (!a.lower && tm > 65535) return GPN_E_UNSUPPORTED;
-  dim3 grid = a.lower ? dim3(tm * (tm + 1) / 2, 1, (unsigned)batch) : dim3(tn, tm, (unsigned)batch);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  int rec = -1;
-  if (profile_on())
-    rec = profile_begin(s, batch * (a.lower ? 8.0 * (0.5 * n * (n + 1.0) + (double)n * d) : 8.0 * ((double)n * m + (double)(n + (symmetric ? 0 : m)) * d)),
-                        PROF_KMAT);
-  switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL(kmat_kernel<GPN_RBF>, grid, dim3(256), 0, s, a); break;
-    case GPN_MATERN52: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, a); break;
-    case GPN_MATERN32: hipLaunchKernelGGL(kmat_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, a); break;
-    case GPN_EXP: hipLaunchKernelGGL(kmat_kernel<GPN_EXP>, grid, dim3(256), 0, s, a); break;
-    case GPN_PERIODIC: hipLaunchKernelGGL(kmat_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, a); break;
-    case GPN_SQDIST: hipLaunchKernelGGL(kmat_kernel<GPN_SQDIST>, grid, dim3(256), 0, s, a); break;
-    default: return -2;
-  }
-  if (rec >= 0) profile_end(s, rec);
-  GPN_LAUNCH_CHECK();
-  return GPN_OK;
+  const KmatArgs a = kmat_args(X, sX, n, X2, sX2, m, d, variance, length_scales, nls, noise, uplo == GPN_LOWER, K, ldk, sK);
+  return kmat_launch<false, true>(static_cast<hipStream_t>(stream), kind, a, batch);
 }
 
 extern "C" int gpn_pack_rhs(void* stream, const double* Y, const double* M, int64_t n, int dy,

@@ -494,19 +494,15 @@ static int lik_derivs_launch(hipStream_t s, int kind, int batch, const double* f
 // the tile sweep of `batch` models and the gather of their rows (n > 0)
 template <int MODE>
 static int lap_rows_launch(hipStream_t s, int kind, int batch, const LapArgs& p, const LapStrides& st, const double* divide, double* out) {
-  if (!kind_is_covariance(kind)) return -2;
   const int64_t t = p.tiles;
   if (t * (t + 1) / 2 > 0x7fffffff || batch > LAP_MAX_BATCH) return GPN_E_UNSUPPORTED;
   const dim3 grid((unsigned)(t * (t + 1) / 2), (unsigned)batch);
-  switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL((lap_rows_kernel<GPN_RBF, MODE>), grid, dim3(256), 0, s, p, st); break;
-    case GPN_MATERN52: hipLaunchKernelGGL((lap_rows_kernel<GPN_MATERN52, MODE>), grid, dim3(256), 0, s, p, st); break;
-    case GPN_MATERN32: hipLaunchKernelGGL((lap_rows_kernel<GPN_MATERN32, MODE>), grid, dim3(256), 0, s, p, st); break;
-    case GPN_EXP: hipLaunchKernelGGL((lap_rows_kernel<GPN_EXP, MODE>), grid, dim3(256), 0, s, p, st); break;
-    case GPN_PERIODIC: hipLaunchKernelGGL((lap_rows_kernel<GPN_PERIODIC, MODE>), grid, dim3(256), 0, s, p, st); break;
-    default: return -2;
-  }
-  GPN_LAUNCH_CHECK();
+  const int rc = with_kind(kind, [&](auto k) -> int {
+    hipLaunchKernelGGL((lap_rows_kernel<decltype(k)::value, MODE>), grid, dim3(256), 0, s, p, st);
+    GPN_LAUNCH_CHECK();
+    return GPN_OK;
+  });
+  if (rc != GPN_OK) return rc;
   hipLaunchKernelGGL(lap_gather_kernel, dim3((unsigned)((p.n + 255) / 256), (unsigned)batch), dim3(256), 0, s, p.work, p.tiles, (int64_t)p.n,
                      divide, out, st.work, st.vec);
   GPN_LAUNCH_CHECK();
@@ -514,9 +510,8 @@ static int lap_rows_launch(hipStream_t s, int kind, int batch, const LapArgs& p,
 }
 
 // the gradient sweep of `batch` models (p.a, p.u, p.d1 set; model b's partials st.work after model 0's) and its reduce into
-// out [batch, 1 + nls]
+// out [batch, 1 + nls] (kind: one that lap_check let through)
 static int lap_grad_launch(hipStream_t s, int kind, int batch, LapArgs p, const LapStrides& st, double* out) {
-  if (!kind_is_covariance(kind)) return -2;       // (before the profile record opens)
   p.nout = 1 + p.nls;
   if (p.n == 0) {
     GPN_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)batch * p.nout * sizeof(double), s));
@@ -526,18 +521,15 @@ static int lap_grad_launch(hipStream_t s, int kind, int batch, LapArgs p, const 
   if (nblocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
   const dim3 grid((unsigned)nblocks, (unsigned)batch);
   const double n = p.n;
-  int rec = -1;
-  if (profile_on()) rec = profile_begin(s, batch * 8.0 * (0.5 * n * (n + 1.0) + n * p.d), PROF_GRAD);
-  switch (kind) {
-    case GPN_RBF: hipLaunchKernelGGL(lap_grad_kernel<GPN_RBF>, grid, dim3(256), 0, s, p, st); break;
-    case GPN_MATERN52: hipLaunchKernelGGL(lap_grad_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, p, st); break;
-    case GPN_MATERN32: hipLaunchKernelGGL(lap_grad_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, p, st); break;
-    case GPN_EXP: hipLaunchKernelGGL(lap_grad_kernel<GPN_EXP>, grid, dim3(256), 0, s, p, st); break;
-    case GPN_PERIODIC: hipLaunchKernelGGL(lap_grad_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, p, st); break;
-    default: return -2;
-  }
-  if (rec >= 0) profile_end(s, rec);
-  GPN_LAUNCH_CHECK();
+  const int rc = with_kind(kind, [&](auto k) -> int {
+    int rec = -1;
+    if (profile_on()) rec = profile_begin(s, batch * 8.0 * (0.5 * n * (n + 1.0) + n * p.d), PROF_GRAD);
+    hipLaunchKernelGGL(lap_grad_kernel<decltype(k)::value>, grid, dim3(256), 0, s, p, st);
+    if (rec >= 0) profile_end(s, rec);
+    GPN_LAUNCH_CHECK();
+    return GPN_OK;
+  });
+  if (rc != GPN_OK) return rc;
   hipLaunchKernelGGL(lap_grad_reduce_kernel, dim3((unsigned)p.nout, (unsigned)batch), dim3(256), 0, s, p.work, nblocks, p.nout, out);
   GPN_LAUNCH_CHECK();
   return GPN_OK;
@@ -574,7 +566,7 @@ extern "C" int gpn_laplace_system(void* stream, int kind, const double* X, int64
   if (!A) return -10;
   if (lda < n) return -11;
   if (n == 0) return GPN_OK;
-  return assemble_laplace_system(static_cast<hipStream_t>(stream), kind, X, n, d, variance, length_scales, nls, sc, A, lda);
+  return assemble_laplace_system_batched(static_cast<hipStream_t>(stream), kind, 1, X, 0, n, d, variance, length_scales, nls, sc, 0, A, lda, 0);
 }
 
 extern "C" int64_t gpn_laplace_rows_work_bytes(int64_t n) {

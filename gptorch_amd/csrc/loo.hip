@@ -436,7 +436,6 @@ static int loo_scale_launch(hipStream_t s, int batch, int64_t n, const double* K
 
 // p: model 0's operands; work holds batch x tiles x nout partials, out [batch, nout]
 static int loo_grad_launch(hipStream_t s, int kind, int batch, LooGradArgs p, const LooGradStrides& st, double* out) {
-  if (kind < GPN_RBF || kind > GPN_PERIODIC) return -2;      // (every kind has a case below; before the profile record opens)
   const int64_t n = p.n, t = loo_tiles(n), nblocks = t * (t + 1) / 2;
   if (nblocks > 0x7fffffff) return GPN_E_UNSUPPORTED;
   const double nn = (double)n;
@@ -446,19 +445,15 @@ static int loo_grad_launch(hipStream_t s, int kind, int batch, LooGradArgs p, co
     q.X += z0 * st.sX; q.variance += z0; q.ls += z0 * p.nls; q.Q += z0 * st.sQ; q.at += z0 * st.sAt; q.wt += z0 * st.sWt;
     q.work += z0 * nblocks * p.nout;
     const dim3 grid((unsigned)nblocks, nb);
-    int rec = -1;
-    if (profile_on()) rec = profile_begin(s, 8.0 * (double)nb * (0.5 * nn * (nn + 1.0) + nn * p.d), PROF_GRAD);
-    switch (kind) {
-      case GPN_RBF: hipLaunchKernelGGL(loo_grad_kernel<GPN_RBF>, grid, dim3(256), 0, s, q, st); break;
-      case GPN_MATERN52: hipLaunchKernelGGL(loo_grad_kernel<GPN_MATERN52>, grid, dim3(256), 0, s, q, st); break;
-      case GPN_MATERN32: hipLaunchKernelGGL(loo_grad_kernel<GPN_MATERN32>, grid, dim3(256), 0, s, q, st); break;
-      case GPN_EXP: hipLaunchKernelGGL(loo_grad_kernel<GPN_EXP>, grid, dim3(256), 0, s, q, st); break;
-      case GPN_SQDIST: hipLaunchKernelGGL(loo_grad_kernel<GPN_SQDIST>, grid, dim3(256), 0, s, q, st); break;
-      case GPN_PERIODIC: hipLaunchKernelGGL(loo_grad_kernel<GPN_PERIODIC>, grid, dim3(256), 0, s, q, st); break;
-      default: return -2;
-    }
-    if (rec >= 0) profile_end(s, rec);
-    GPN_LAUNCH_CHECK();
+    const int rc = with_kind<true>(kind, [&](auto k) -> int {
+      int rec = -1;
+      if (profile_on()) rec = profile_begin(s, 8.0 * (double)nb * (0.5 * nn * (nn + 1.0) + nn * p.d), PROF_GRAD);
+      hipLaunchKernelGGL(loo_grad_kernel<decltype(k)::value>, grid, dim3(256), 0, s, q, st);
+      if (rec >= 0) profile_end(s, rec);
+      GPN_LAUNCH_CHECK();
+      return GPN_OK;
+    });
+    if (rc != GPN_OK) return rc;
     hipLaunchKernelGGL(loo_grad_reduce_kernel, dim3((unsigned)p.nout, nb), dim3(256), 0, s, q.work, nblocks, p.nout, out + z0 * p.nout);
     GPN_LAUNCH_CHECK();
   }

@@ -615,6 +615,16 @@ static int refine_gather_finish(hipStream_t s, const double* Y, const double* M,
   return GPN_OK;
 }
 
+// the residual pass over the lower tiles p.q_off .. p.q_off + grid.x - 1 (one or RDY right-hand sides at a time)
+static int resid_sym_launch(hipStream_t s, int kind, const RefineSymArgs& p, dim3 grid) {
+  return with_kind(kind, [&](auto k) -> int {
+    if (p.dy == 1) hipLaunchKernelGGL((refine_resid_sym_kernel<decltype(k)::value, 1>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((refine_resid_sym_kernel<decltype(k)::value, RDY>), grid, dim3(256), 0, s, p);
+    GPN_LAUNCH_CHECK();
+    return GPN_OK;
+  });
+}
+
 extern "C" int gpn_lml_refine(void* stream, int kind, const double* X, int64_t n, int d,
                               const double* Y, const double* M, int dy,
                               const double* variance, const double* length_scales, int nls, const double* noise,
@@ -643,22 +653,8 @@ extern "C" int gpn_lml_refine(void* stream, int kind, const double* X, int64_t n
   p.X = X; p.variance = variance; p.ls = length_scales; p.noise = noise; p.a = work + L.a;
   p.prow = work + L.prow; p.pcol = work + L.pcol; p.lds = L.lds;
   p.n = (int)n; p.d = d; p.nls = nls; p.dy = dy; p.q_off = 0;
-  const dim3 grid((unsigned)(ntile * (ntile + 1) / 2));
-#define GPN_RESID(KIND)                                                                                 \
-  do {                                                                                                  \
-    if (dy == 1) hipLaunchKernelGGL((refine_resid_sym_kernel<KIND, 1>), grid, dim3(256), 0, s, p);      \
-    else hipLaunchKernelGGL((refine_resid_sym_kernel<KIND, RDY>), grid, dim3(256), 0, s, p);            \
-  } while (0)
-  switch (kind) {
-    case GPN_RBF: GPN_RESID(GPN_RBF); break;
-    case GPN_MATERN52: GPN_RESID(GPN_MATERN52); break;
-    case GPN_MATERN32: GPN_RESID(GPN_MATERN32); break;
-    case GPN_EXP: GPN_RESID(GPN_EXP); break;
-    case GPN_PERIODIC: GPN_RESID(GPN_PERIODIC); break;
-    default: return -2;
-  }
-#undef GPN_RESID
-  GPN_LAUNCH_CHECK();
+  rc = resid_sym_launch(s, kind, p, dim3((unsigned)(ntile * (ntile + 1) / 2)));
+  if (rc != GPN_OK) return rc;
   return refine_gather_finish(s, Y, M, n, dy, work, L, out3);
 }
 
@@ -794,22 +790,8 @@ extern "C" int gpn_refine_resid_part(void* stream, int kind, const double* X, in
   p.prow = work; p.pcol = work + cnt * dy * RT * 2; p.lds = lds;
   p.n = (int)n; p.d = d; p.nls = nls; p.dy = dy; p.q_off = (int)q0;
   if (cnt > 0) {
-    const dim3 grid((unsigned)cnt);
-#define GPN_RESID(KIND)                                                                                 \
-  do {                                                                                                  \
-    if (dy == 1) hipLaunchKernelGGL((refine_resid_sym_kernel<KIND, 1>), grid, dim3(256), 0, s, p);      \
-    else hipLaunchKernelGGL((refine_resid_sym_kernel<KIND, RDY>), grid, dim3(256), 0, s, p);            \
-  } while (0)
-    switch (kind) {
-      case GPN_RBF: GPN_RESID(GPN_RBF); break;
-      case GPN_MATERN52: GPN_RESID(GPN_MATERN52); break;
-      case GPN_MATERN32: GPN_RESID(GPN_MATERN32); break;
-      case GPN_EXP: GPN_RESID(GPN_EXP); break;
-      case GPN_PERIODIC: GPN_RESID(GPN_PERIODIC); break;
-      default: return -2;
-    }
-#undef GPN_RESID
-    GPN_LAUNCH_CHECK();
+    const int rc = resid_sym_launch(s, kind, p, dim3((unsigned)cnt));
+    if (rc != GPN_OK) return rc;
   }
   hipLaunchKernelGGL(refine_gather_kernel, dim3((unsigned)ntile, (unsigned)dy), dim3(256), 0, s, p.prow, p.pcol, (int)ntile, dy, lds, n, ka,
                      q0, q1);

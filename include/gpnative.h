@@ -87,7 +87,9 @@ int64_t gpn_winv_bytes(int64_t n);
  * variance[1], length_scales[nls] (nls = 1 or d), noise[1] or NULL: device scalars
  * in CONSTRAINED space.  uplo = GPN_LOWER (only with X2 == NULL) writes tiles on
  * or below the diagonal only.  Distances are direct differences (no Gram trick),
- * so r^2 >= 0 by construction (the clamp of util.py:88 is the identity).  kind: all six (GPN_SQDIST: K = r^2). */
+ * so r^2 >= 0 by construction (the clamp of util.py:88 is the identity).  kind: all six (GPN_SQDIST: K = r^2).
+ * uplo = GPN_FULL with more than 65535 * 64 rows (the row tiles are a grid dimension): GPN_E_UNSUPPORTED, as in the
+ * lock-step form. */
 /* kind: all six, GPN_SQDIST included (table at GPN_FULL above). */
 int gpn_kernel_matrix(void* stream, int kind,
                       const double* X, int64_t n, const double* X2, int64_t m, int d,

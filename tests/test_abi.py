@@ -162,6 +162,129 @@ def test_kind_validation_without_launch():
         assert lib.gpn_kernel_matrix(null, kind, null, 4, null, 4, 2, null, null, 1, null, 0, null, 4) == (-3 if kind == 4 else -2)
 
 
+P = "P"     # in the table below: a pointer that is never followed
+
+# (entry point, an argument list that is valid throughout, [({argument index (stream = 0): invalid value, ...}, status), ...]).
+# Every case is refused by host-side validation, so none reaches a HIP call: where a kind is SERVED (GPN_SQDIST = 4 by the
+# assembly and the sweeps) it is paired with a null output, the last argument checked -- the status then shows that the kind got
+# past every other check.  The grad.hip entries resolve the kind last: a bad kind with a null X is the null X's status there.
+_STATUS_TABLE = [
+    ("gpn_kernel_matrix", [None, 0, P, 4, P, 4, 2, P, P, 1, P, 0, P, 4], [
+        ({2: None}, -3), ({3: -1}, -4), ({5: -1}, -6), ({6: 0}, -7), ({7: None}, -8), ({8: None}, -9), ({9: 3}, -10), ({11: 7}, -12),
+        ({11: 1}, -12), ({12: None}, -13), ({13: 3}, -14), ({1: -1}, -2), ({1: 6}, -2), ({1: 4, 12: None}, -13), ({1: -1, 2: None}, -2),
+    ]),
+    ("gpn_kernel_matrix_batched", [None, 0, 2, P, 0, 4, P, 0, 4, 2, P, P, 1, P, 0, P, 4, 16], [
+        ({2: 0}, -3), ({2: 65536}, -3), ({3: None}, -4), ({5: -1}, -6), ({8: -1}, -9), ({9: 0}, -10), ({10: None}, -11), ({11: None}, -12),
+        ({12: 3}, -13), ({14: 7}, -15), ({14: 1}, -15), ({15: None}, -16), ({16: 3}, -17), ({17: 15}, -18), ({1: -1}, -2), ({1: 6}, -2),
+        ({1: 4, 15: None}, -16), ({1: -1, 3: None}, -2),
+    ]),
+    ("gpn_lml_grad", [None, 0, P, 4, 2, P, P, 1, P, 4, P, 4, 1, P, P], [
+        ({2: None}, -3), ({3: 0}, -4), ({4: 0}, -5), ({5: None}, -6), ({6: None}, -7), ({7: 3}, -8), ({8: None}, -9), ({9: 3}, -10),
+        ({10: None}, -11), ({11: 3}, -12), ({12: 0}, -13), ({13: None}, -14), ({14: None}, -15), ({1: -1}, -2), ({1: 6}, -2),
+        ({1: 4, 14: None}, -15), ({1: -1, 2: None}, -3),
+    ]),
+    ("gpn_lml_grad_batched", [None, 0, 2, P, 0, 4, 2, P, P, 1, P, 4, 16, P, 4, 4, 1, P, P], [
+        ({2: 0}, -3), ({2: 65536}, -102), ({3: None}, -4), ({5: 0}, -6), ({6: 0}, -7), ({7: None}, -8), ({8: None}, -9), ({9: 3}, -10),
+        ({10: None}, -11), ({11: 3}, -12), ({13: None}, -14), ({14: 3}, -15), ({16: 0}, -17), ({17: None}, -18), ({18: None}, -19),
+        ({1: -1}, -2), ({1: 6}, -2), ({1: 4, 18: None}, -19), ({1: -1, 3: None}, -4),
+    ]),
+    ("gpn_kernel_grad", [None, 0, P, 4, P, 4, 2, P, P, 1, P, 4, P, P], [
+        ({2: None}, -3), ({3: 0}, -4), ({5: 0}, -6), ({6: 0}, -7), ({7: None}, -8), ({8: None}, -9), ({9: 3}, -10), ({10: None}, -11),
+        ({11: 3}, -12), ({12: None}, -13), ({13: None}, -14), ({1: -1}, -2), ({1: 6}, -2), ({1: 4, 13: None}, -14), ({1: -1, 2: None}, -3),
+    ]),
+    ("gpn_kernel_grad_batched", [None, 0, 2, P, 0, 4, P, 0, 4, 2, P, P, 1, P, 4, 16, P, P], [
+        ({2: 0}, -3), ({2: 65536}, -3), ({3: None}, -4), ({5: 0}, -6), ({8: 0}, -9), ({9: 0}, -10), ({10: None}, -11), ({11: None}, -12),
+        ({12: 3}, -13), ({13: None}, -14), ({14: 3}, -15), ({16: None}, -17), ({17: None}, -18), ({1: -1}, -2), ({1: 6}, -2),
+        ({1: 4, 17: None}, -18), ({1: -1, 3: None}, -4),
+    ]),
+    ("gpn_kernel_grad_x2", [None, 0, P, 4, P, 4, 2, P, P, 1, P, 4, 1.0, 0, P, P], [
+        ({2: None}, -3), ({3: 0}, -4), ({4: None}, -5), ({5: 0}, -6), ({6: 0}, -7), ({6: 1048561}, -7), ({7: None}, -8), ({8: None}, -9),
+        ({9: 3}, -10), ({10: None}, -11), ({11: 3}, -12), ({14: None}, -15), ({15: None}, -16), ({1: -1}, -2), ({1: 6}, -2),
+        ({1: 4, 15: None}, -16), ({1: -1, 2: None}, -3),
+    ]),
+    # (batch = 1 and d > 64 go model by model through the single form)
+    ("gpn_kernel_grad_x2_batched", [None, 0, 2, P, 0, 4, P, 0, 4, 2, P, P, 1, P, 4, 16, 1.0, 0, P, P], [
+        ({2: 0}, -3), ({2: 65536}, -3), ({3: None}, -4), ({5: 0}, -6), ({6: None}, -7), ({8: 0}, -9), ({9: 0}, -10), ({9: 1048561}, -10),
+        ({10: None}, -11), ({11: None}, -12), ({12: 3}, -13), ({13: None}, -14), ({14: 3}, -15), ({18: None}, -19), ({19: None}, -20),
+        ({1: -1}, -2), ({1: 6}, -2), ({1: 4, 19: None}, -20), ({1: -1, 3: None}, -4), ({1: -1, 2: 1}, -2), ({1: 6, 9: 65}, -2),
+    ]),
+    ("gpn_lml_refine", [None, 0, P, 4, 2, P, P, 1, P, P, 1, P, P, 128, P, P, P], [
+        ({2: None}, -3), ({3: -1}, -4), ({4: 0}, -5), ({5: None}, -6), ({7: 0}, -8), ({8: None}, -9), ({9: None}, -9), ({10: 3}, -11),
+        ({11: None}, -12), ({12: None}, -13), ({13: 4}, -14), ({14: None}, -15), ({15: None}, -16), ({16: None}, -17), ({1: -1}, -2),
+        ({1: 4}, -2), ({1: 6}, -2),
+    ]),
+    ("gpn_refine_resid_part", [None, 0, P, 4, 2, P, P, 1, P, P, 1, 0, 1, P, P], [
+        ({2: None}, -3), ({3: 0}, -4), ({4: 0}, -5), ({5: None}, -6), ({6: None}, -6), ({7: 3}, -8), ({8: None}, -9), ({9: None}, -10),
+        ({10: 0}, -11), ({11: -1}, -12), ({12: 2}, -12), ({11: 1, 12: 0}, -12), ({13: None}, -14), ({14: None}, -15), ({1: -1}, -2),
+        ({1: 4}, -2), ({1: 6}, -2),
+    ]),
+    ("gpn_laplace_system", [None, 0, P, 4, 2, P, P, 1, P, P, 4], [
+        ({2: None}, -3), ({3: -1}, -4), ({3: 2147483648}, -4), ({4: 0}, -5), ({5: None}, -6), ({6: None}, -7), ({7: 3}, -8),
+        ({8: None}, -9), ({9: None}, -10), ({10: 3}, -11), ({1: -1}, -2), ({1: 4}, -2), ({1: 6}, -2),
+    ]),
+    ("gpn_laplace_matvec", [None, 0, P, 4, 2, P, P, 1, P, P, P], [
+        ({2: None}, -3), ({3: -1}, -4), ({3: 2147483648}, -4), ({4: 0}, -5), ({5: None}, -6), ({6: None}, -7), ({7: 3}, -8),
+        ({8: None}, -9), ({9: None}, -10), ({10: None}, -11), ({1: -1}, -2), ({1: 4}, -2), ({1: 6}, -2),
+    ]),
+    ("gpn_laplace_diag", [None, 0, P, 4, 2, P, P, 1, P, P, 4, P, P], [
+        ({2: None}, -3), ({3: -1}, -4), ({3: 2147483648}, -4), ({4: 0}, -5), ({5: None}, -6), ({6: None}, -7), ({7: 3}, -8),
+        ({8: None}, -9), ({9: None}, -10), ({10: 3}, -11), ({11: None}, -12), ({12: None}, -13), ({1: -1}, -2), ({1: 4}, -2), ({1: 6}, -2),
+    ]),
+    ("gpn_laplace_grad", [None, 0, P, 4, 2, P, P, 1, P, P, 4, P, P, P, P, P], [
+        ({2: None}, -3), ({3: -1}, -4), ({3: 2147483648}, -4), ({4: 0}, -5), ({5: None}, -6), ({6: None}, -7), ({7: 3}, -8),
+        ({8: None}, -9), ({9: None}, -10), ({10: 3}, -11), ({11: None}, -12), ({12: None}, -13), ({13: None}, -14), ({14: None}, -15),
+        ({15: None}, -16), ({1: -1}, -2), ({1: 4}, -2), ({1: 6}, -2),
+    ]),
+    ("gpn_laplace_system_batched", [None, 0, 2, P, 0, 4, 2, P, P, 1, P, 4, P, 4, 16], [
+        ({2: 0}, -3), ({3: None}, -4), ({4: -1}, -5), ({5: -1}, -6), ({5: 2147483648}, -6), ({6: 0}, -7), ({7: None}, -8), ({8: None}, -9),
+        ({9: 3}, -10), ({10: None}, -11), ({11: -1}, -12), ({12: None}, -13), ({13: 3}, -14), ({14: 15}, -15), ({2: 65536}, -102),
+        ({1: -1}, -2), ({1: 4}, -2), ({1: 6}, -2),
+    ]),
+    ("gpn_laplace_matvec_batched", [None, 0, 2, P, 0, 4, 2, P, P, 1, P, 4, P, P], [
+        ({2: 0}, -3), ({3: None}, -4), ({4: -1}, -5), ({5: -1}, -6), ({5: 2147483648}, -6), ({6: 0}, -7), ({7: None}, -8), ({8: None}, -9),
+        ({9: 3}, -10), ({10: None}, -11), ({11: -1}, -12), ({12: None}, -13), ({13: None}, -14), ({2: 65536}, -102), ({1: -1}, -2),
+        ({1: 4}, -2), ({1: 6}, -2),
+    ]),
+    ("gpn_laplace_diag_batched", [None, 0, 2, P, 0, 4, 2, P, P, 1, P, 4, P, 4, 16, P, P], [
+        ({2: 0}, -3), ({3: None}, -4), ({4: -1}, -5), ({5: -1}, -6), ({5: 2147483648}, -6), ({6: 0}, -7), ({7: None}, -8), ({8: None}, -9),
+        ({9: 3}, -10), ({10: None}, -11), ({11: -1}, -12), ({12: None}, -13), ({13: 3}, -14), ({14: -1}, -15), ({15: None}, -16),
+        ({16: None}, -17), ({2: 65536}, -102), ({1: -1}, -2), ({1: 4}, -2), ({1: 6}, -2),
+    ]),
+    ("gpn_laplace_grad_batched", [None, 0, 2, P, 0, 4, 2, P, P, 1, P, P, 4, 16, P, P, P, 4, P, P], [
+        ({2: 0}, -3), ({3: None}, -4), ({4: -1}, -5), ({5: -1}, -6), ({5: 2147483648}, -6), ({6: 0}, -7), ({7: None}, -8), ({8: None}, -9),
+        ({9: 3}, -10), ({10: None}, -11), ({11: None}, -12), ({12: 3}, -13), ({13: -1}, -14), ({14: None}, -15), ({15: None}, -16),
+        ({16: None}, -17), ({17: -1}, -18), ({18: None}, -19), ({19: None}, -20), ({2: 65536}, -102), ({1: -1}, -2), ({1: 4}, -2),
+        ({1: 6}, -2),
+    ]),
+    ("gpn_loo_grad", [None, 0, P, 4, 2, P, P, 1, P, 4, P, 4, P, 4, 1, P, 1048576, P], [
+        ({2: None}, -3), ({3: -1}, -4), ({3: 2147483648}, -4), ({4: 0}, -5), ({5: None}, -6), ({6: None}, -7), ({7: 3}, -8),
+        ({8: None}, -9), ({9: 3}, -10), ({10: None}, -11), ({11: 3}, -12), ({12: None}, -13), ({13: 3}, -14), ({14: 0}, -15),
+        ({15: None}, -16), ({16: 0}, -17), ({17: None}, -18), ({1: -1}, -2), ({1: 6}, -2), ({1: 4, 17: None}, -18),
+    ]),
+    ("gpn_loo_grad_batched", [None, 0, 2, P, 0, 4, 2, P, P, 1, P, 4, 16, P, 4, 4, P, 4, 4, 1, P, 1048576, P], [
+        ({2: 0}, -3), ({3: None}, -4), ({4: 3}, -5), ({5: -1}, -6), ({6: 0}, -7), ({7: None}, -8), ({8: None}, -9), ({9: 3}, -10),
+        ({10: None}, -11), ({11: 3}, -12), ({12: 15}, -13), ({13: None}, -14), ({14: 3}, -15), ({15: 3}, -16), ({16: None}, -17),
+        ({17: 3}, -18), ({18: 3}, -19), ({19: 0}, -20), ({20: None}, -21), ({21: 0}, -22), ({22: None}, -23), ({1: -1}, -2), ({1: 6}, -2),
+        ({1: 4, 22: None}, -23),
+    ]),
+]
+
+
+@pytest.mark.parametrize("name,valid,cases", _STATUS_TABLE, ids=[row[0] for row in _STATUS_TABLE])
+def test_validation_status_table(name, valid, cases):
+    """the kind-dispatched entry points, single and lock-step: each checked argument invalidated in turn (the others valid) and
+    kind in {-1, 4, 6} give the status written here -- the numbers are part of the C ABI and no launch precedes them."""
+    fn = getattr(_native.lib(), name)
+    cell = ctypes.c_double(0.0)
+    stand_in = ctypes.cast(ctypes.pointer(cell), ctypes.c_void_p)
+    for override, want in cases:
+        assert want < 0                                  # (a case that passed validation would launch)
+        args = [stand_in if v is P else v for v in valid]
+        for pos, v in override.items():
+            args[pos] = v
+        assert fn(*args) == want, (name, override)
+
+
 def test_missing_library_fails_loudly(monkeypatch, tmp_path):
     monkeypatch.setattr(_native, "_lib", None)
     monkeypatch.setattr(_native, "LIB_PATH", str(tmp_path / "nope.so"))
